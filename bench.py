@@ -24,11 +24,16 @@ the /opt/rocm builds the tests use; the JSON line records the mapped
 libamdhip64 / librccl paths and the library's SHA-256, and `roofline.traffic`
 is taken only from a PMC profile of that same library build.
 
-Prints ONE JSON line on rank 0 (contract in the task brief), including
-`roofline` (dominant kernel vs the v_mad_u64_u32 peak) and `cpu_baseline`
-(CPU ports on a bounded sample: the 64-bit-limb restatement
-tests/hostemu/cpu64_verify.cpp as the main value, the kernels' 32-bit-limb
-algorithms for the host, tests/hostemu/cpu_verify.cpp, as "alt").
+Prints ONE JSON line on rank 0, including `roofline` (dominant kernel vs the
+v_mad_u64_u32 peak, from the HIP events of the timed steps themselves).  A
+plain run does only what that line's headline figure needs: set-up, warm-up,
+the timed steps, the check of the last step's codes.  `--full` adds the legs
+that take runs of their own: `cpu_baseline` (CPU ports on a bounded sample: the
+64-bit-limb restatement tests/hostemu/cpu64_verify.cpp as the main value, the
+kernels' 32-bit-limb algorithms for the host, tests/hostemu/cpu_verify.cpp, as
+"alt") and `host_buffers` (the same records from host buffers); both are null
+without it.  `--dump-outputs DIR` writes the last timed step's outputs (codes,
+verdict bits; signatures in sign mode) as DIR/<name>.npy.
 """
 import argparse
 import hashlib
@@ -63,7 +68,15 @@ def parse():
     ap.add_argument("--n", type=int, default=None,
                     help="signatures per GPU (default: 1,048,576 at N=1 = config[1]; 2,097,152 at N>1 = config[2])")
     ap.add_argument("--forged-frac", type=float, default=0.0)
-    ap.add_argument("--cpu-sample", type=int, default=40960, help="records for the CPU baseline (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines (--cpu-sample) and the "
+                         "host-buffer steps (--host-steps).  Off by default: a plain run sets up, warms up, times "
+                         "--steps steps and prints the result line, with cpu_baseline and host_buffers null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (verdict codes, verdict "
+                         "bits, signatures) to DIR/<name>.npy as float32; above 64 MB in all, a fixed seeded sample")
+    ap.add_argument("--cpu-sample", type=int, default=40960,
+                    help="with --full: records for the CPU baseline (0: skip)")
     ap.add_argument("--cpu-threads", type=int, default=min(16, os.cpu_count() or 1),
                     help="host threads for the CPU baseline (the GPU box's CPU share is 16)")
     ap.add_argument("--mode", choices=["persig", "rlc", "rlcd", "adversarial", "keyed", "rsa", "sign"], default="persig",
@@ -73,8 +86,8 @@ def parse():
                          "PKCS#1 v1.5 raw verify (cp_enclave_verify::verify_rsa) over 32-byte messages; sign: SURVEY §8(f) "
                          "rank 3, batch PrivateKey::sign")
     ap.add_argument("--host-steps", type=int, default=2,
-                    help="N=1 persig: extra steps from host buffers (cess_bls_verify_batch incl. PCIe), reported as "
-                         "host_buffers_sigs_per_s beside the device-resident value (0: skip)")
+                    help="with --full, N=1 persig: extra steps from host buffers (cess_bls_verify_batch incl. PCIe), "
+                         "reported as host_buffers_sigs_per_s beside the device-resident value (0: skip)")
     ap.add_argument("--keys", type=int, default=16, help="distinct keys (rlc / keyed modes)")
     ap.add_argument("--forged-count", type=int, default=0, help="forgeries per rank (rlc mode)")
     ap.add_argument("--dry-run", action="store_true",
@@ -241,6 +254,34 @@ def lib_sha256() -> str:
     p = os.path.join(ROOT, "cess_amd", "lib", "libcess_bls.so")
     with open(p, "rb") as f:
         return hashlib.sha256(f.read()).hexdigest()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the last timed step returned to its caller, one
+    float32 DIR/<name>.npy per array (bytes and bits are exact in float32).
+    The arrays share DUMP_BUDGET_BYTES equally; a larger one is cut to a fixed
+    seeded sample of its elements (sorted indices, the same for every run and
+    build), so two builds run with the same flags compare output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            pick = np.random.default_rng((0xD0, a.size)).choice(a.size, size=cap, replace=False)
+            pick.sort()
+            a = a[pick]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
+
+
+def verdict_bits(words, n):
+    """Bit i of the verdict bitmap (uint64 words, little-endian bit order) as
+    one 0/1 byte per record."""
+    import numpy as np
+    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:n]
 
 
 # resident waves per SIMD of the two Fp12 kernels, fixed by their LDS images:
@@ -467,6 +508,8 @@ def run_rsa(args, ctx, rank, world):
     st = {k: v for k, v in ctx.stage_stats(reset=True).items() if v[1] > 0}
     codes = np.frombuffer(ctx.from_device(d_codes, n), dtype=np.uint8)
     ok = bool((codes == expect).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"codes": codes})
     if world > 1:
         elapsed = ctx.comm_max(elapsed)
         ok = ctx.comm_max(0.0 if ok else 1.0) == 0.0
@@ -481,7 +524,7 @@ def run_rsa(args, ctx, rank, world):
         pmc = load_pmc_traffic(sha, "k_rsa_verify_2048u", n)
         kd = (pmc or {}).get("all", {}).get("k_rsa_verify_2048u", {})
         cpu = None
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             kn, ke = bls_rsa_key(key)
             cpu = cpu_baseline_rsa([(bytes(M[i]), bytes(S[i])) for i in range(256)], kn, ke, min(args.cpu_sample, 20000))
         print(json.dumps({
@@ -554,6 +597,8 @@ def run_sign(args, ctx, rank, world):
         ctx.comm_barrier()
     elapsed = time.perf_counter() - t0
     st = {k: v for k, v in ctx.stage_stats(reset=True).items() if v[1] > 0}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"signatures": np.frombuffer(ctx.from_device(d_sig, 48 * n), dtype=np.uint8)})
     # untimed: the signatures verify against keys from the keygen kernel
     pks = ctx.public_keys_raw(sk.tobytes())
     d_pk = ctx.to_device(np.frombuffer(pks, dtype=np.uint8))
@@ -705,6 +750,9 @@ def run_rlc(args, ctx, rank, world):
     expect = np.zeros(n, dtype=np.uint8)
     expect[forged] = 5
     ok = bool((np.frombuffer(codes, dtype=np.uint8) == expect).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"codes": np.frombuffer(codes, dtype=np.uint8),
+                                         "verdict_bits": verdict_bits(np.array(words, dtype=np.uint64), n)})
     if world > 1:
         elapsed = ctx.comm_max(elapsed)
         ok = ctx.comm_max(0.0 if ok else 1.0) == 0.0
@@ -873,12 +921,21 @@ def main():
     popcount = int(np.unpackbits(words.view(np.uint8)).sum())
     ok = local_ok if world == 1 else ctx.comm_max(0.0 if local_ok else 1.0) == 0.0
     # `comm`: what the communicator itself reported at setup (comm_setup)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's codes and bitmap, as the caller's buffers hold
+        # them: the whole batch (every rank's shard, gathered) at N > 1
+        if world > 1:
+            all_codes = codes_all.reshape(world, wpr * 64)[:, :n].reshape(-1)
+            all_bits = np.concatenate([verdict_bits(w, n) for w in words.reshape(world, wpr)])
+        else:
+            all_codes, all_bits = my, verdict_bits(words, n)
+        dump_outputs(args.dump_outputs, {"codes": all_codes, "verdict_bits": all_bits})
 
     # the same records from HOST buffers (cess_bls_verify_batch: H2D copies,
     # the pipeline, D2H of codes + bitmap), as node callers pass them; reported
-    # beside the device-resident `value`, never as it
+    # beside the device-resident `value`, never as it (--full only)
     host_rate = None
-    if world == 1 and args.mode == "persig" and args.host_steps > 0:
+    if args.full and world == 1 and args.mode == "persig" and args.host_steps > 0:
         o_host = np.arange(n + 1, dtype=np.uint64) * 32
         ctx.synchronize()
         th = time.perf_counter()
@@ -918,7 +975,7 @@ def main():
             if kd.get("SQ_WAVE_CYCLES"):
                 valu_active = kd.get("SQ_ACTIVE_INST_VALU", 0.0) / kd["SQ_WAVE_CYCLES"]
         cpu = None
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             import random
             rr = random.Random(5)
             idx = rr.sample(range(n), min(n, args.cpu_sample))

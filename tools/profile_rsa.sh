@@ -22,5 +22,5 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU
   echo "pmc pass $i rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 $OUT/pmc_p$i.log; exit $rc; fi
 done
-timeout -k 10 300 python3 bench.py --mode rsa --n $N --steps 5 --warmup 1 --cpu-sample 20000 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --mode rsa --n $N --steps 5 --warmup 1 --full --cpu-sample 20000 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; cat $OUT/bench.json; exit $rc
