@@ -388,16 +388,14 @@ CESS_HD fph pcyc_z0(const fph& z1, const fph& z2, const fph& z3, const fph& z4, 
   return add(mul_nr(add(dbl(psqr(z1)), pdot2(z2, z5, neg(mul3(z3)), z4))), fph_one());
 }
 
-// FE_CHAIN (staged.hpp cyc_chain): the powers a^(2^k), k = 16, 48, 57, 60, 62,
-// 63, of the cyclotomic element in `base` into the stores X(0..5).
-// CESS_CHAIN_TAIL (staged.hpp, default 1): only a^(2^16), a^(2^48) and
-// a^(2^57) come from the compressed run and its decompression; a^(2^60),
-// a^(2^62) and a^(2^63) follow from a^(2^57) by 3 + 2 + 1 Granger-Scott
-// squarings.  Per exponentiation by x that is 6 GS squarings (6 products each,
-// against 4 for a Karabina squaring) for 3 decompressions (~8.5 products each).
+// FE_CHAIN (staged.hpp cyc_chain): the powers a^(2^k), k = 16, 48, 57, of the
+// cyclotomic element in `base` into the stores X(0..2), from one compressed run
+// of 57 squarings and its decompression (~8.5 products per power).
+// CESS_FE_CYCEXP (staged.hpp) builds a^|x| from them with 7 Granger-Scott
+// squarings and four Fp12 products.
 template <class B, class XFn>
 CESS_HD void pcyc_chain(const B& base, XFn&& X) {
-  constexpr int ND = CESS_CHAIN_TAIL ? 3 : 6;   // decompressed powers
+  constexpr int ND = 3;   // decompressed powers
 #ifndef CESS_PAIR_KCYC_PS
 #define CESS_PAIR_KCYC_PS 1
 #endif
@@ -410,7 +408,7 @@ CESS_HD void pcyc_chain(const B& base, XFn&& X) {
     int k = 0;
 #pragma unroll 1
     for (int j = 0; j < ND; j++) {
-      const int stop = j == 0 ? 16 : j == 1 ? 48 : j == 2 ? 57 : j == 3 ? 60 : j == 4 ? 62 : 63;
+      const int stop = j == 0 ? 16 : j == 1 ? 48 : 57;
       pkcyc_run_ps(u, w, stop - k);
       k = stop;
       CESS_MEMBAR();
@@ -425,7 +423,7 @@ CESS_HD void pcyc_chain(const B& base, XFn&& X) {
     int k = 0;
 #pragma unroll 1
     for (int j = 0; j < ND; j++) {
-      const int stop = j == 0 ? 16 : j == 1 ? 48 : j == 2 ? 57 : j == 3 ? 60 : j == 4 ? 62 : 63;
+      const int stop = j == 0 ? 16 : j == 1 ? 48 : 57;
       pkcyc_run(z2, z3, z4, z5, stop - k);
       k = stop;
       CESS_MEMBAR();
@@ -466,35 +464,15 @@ CESS_HD void pcyc_chain(const B& base, XFn&& X) {
     x.st(0, pcyc_z0(z1, x.ld(3), x.ld(2), x.ld(1), x.ld(5)));
     CESS_MEMBAR();
   }
-  if (degen) {   // pair-uniform; Granger-Scott squarings with X(5) as the running power
-    const auto w = X(5);
+  if (degen) {   // pair-uniform; Granger-Scott squarings with X(2) as the running power
+    const auto w = X(2);
     pcopy12(w, base);
 #pragma unroll 1
-    for (int j = 0; j < 5; j++) {
-      const int run = j == 0 ? 16 : j == 1 ? 32 : j == 2 ? 9 : j == 3 ? 3 : 2;
-      pcyc_square_run(w, run);
-      pcopy12(X(j), w);
-    }
-    pcyc_square_run(w, 1);
-  }
-#if CESS_CHAIN_TAIL
-  else {   // X3..X5 from X2 = a^(2^57): 3, 2, 1 squarings
-    fph z[6];
-    {
-      const auto x2 = X(2);
-#pragma unroll
-      for (int k = 0; k < 6; k++) z[k] = x2.ld(k);
-    }
-#pragma unroll 1
-    for (int j = 3; j < 6; j++) {
-      pcyc_square_regs(z, j == 3 ? 3 : j == 4 ? 2 : 1);
-      CESS_MEMBAR();
-      const auto x = X(j);
-#pragma unroll
-      for (int k = 0; k < 6; k++) x.st(k, z[k]);
+    for (int j = 0; j < ND; j++) {
+      pcyc_square_run(w, j == 0 ? 16 : j == 1 ? 32 : 9);
+      if (j < ND - 1) pcopy12(X(j), w);
     }
   }
-#endif
 }
 
 // The program (staged.hpp final_exp_staged) on ONE in-place accumulator

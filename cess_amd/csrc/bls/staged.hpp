@@ -548,25 +548,40 @@ CESS_HD void inv12_stream(const D& d, const S& f, const T& t) {
 // x are spelled out as square runs and multiplies by the base.
 // ---------------------------------------------------------------------------
 enum FeOp : uint8_t { FE_LOAD, FE_STORE, FE_MUL, FE_SQN, FE_CONJ, FE_FROB, FE_INV, FE_CHAIN, FE_END };
-// SL_TM: FE_MUL's Fp6 temporary when the park caches its first operand
-// (CESS_FE_APARK)
+// SL_X0..SL_X2: FE_CHAIN's powers; SL_XT: the intermediate power of
+// CESS_FE_CYCEXP; SL_TM: FE_MUL's Fp6 temporary when the park caches its first
+// operand (CESS_FE_APARK)
 enum FeSlot : uint8_t { SL_F = 0, SL_M, SL_T0, SL_T1, SL_T3, SL_T4, SL_T5, SL_T6,
-                        SL_X0, SL_X1, SL_X2, SL_X3, SL_X4, SL_X5, SL_TM, SL_N };
+                        SL_X0, SL_X1, SL_X2, SL_XT, SL_TM, SL_N };
 
-// a^x (x = -0xd201000000010000) for a in slot s: |x| has bits 63, 62, 60, 57,
-// 48, 16, so a^|x| = a^(2^63) a^(2^62) a^(2^60) a^(2^57) a^(2^48) a^(2^16).
-// FE_CHAIN s runs the 63 squarings in Karabina's compressed form and leaves
-// the six powers, decompressed with one Fp2 inversion, in slots X5..X0; five
-// multiplies and the conjugation (x < 0) follow.
-#define CESS_FE_CYCEXP(s) \
-  {FE_CHAIN, s}, {FE_LOAD, SL_X5}, {FE_MUL, SL_X4}, {FE_MUL, SL_X3}, {FE_MUL, SL_X2}, {FE_MUL, SL_X1}, \
-      {FE_MUL, SL_X0}, {FE_CONJ, 0}
+// a^|x| for a in slot s (x = -0xd201000000010000):
+//   |x| = 2^16 + 2^48 + 105 2^57,  105 = (8 - 1)(16 - 1).
+// FE_CHAIN s runs 57 squarings in Karabina's compressed form and leaves
+// X0, X1, X2 = a^(2^16), a^(2^48), a^(2^57), decompressed with one Fp2
+// inversion.  In the cyclotomic subgroup an inverse is a conjugation, so with
+// b = X2
+//   t = b^8 conj(b) = b^7,   y = t^16 conj(t) = t^15 = b^105,   a^|x| = y X1 X0:
+// 3 + 4 Granger-Scott squarings and four products (the six powers 2^16, 2^48,
+// 2^57, 2^60, 2^62, 2^63 multiplied together took 6 squarings and five).  A
+// product by a conjugate is acc conj(g) = conj(conj(acc) g); the program keeps
+// u = conj(t) = conj(b^8) b (slot XT), and conj(u^16) u = t^16 conj(t) = y.
+#define CESS_FE_CYCEXP_ABS(s)                                                                                      \
+  {FE_CHAIN, s}, {FE_LOAD, SL_X2}, {FE_SQN, 3}, {FE_CONJ, 0}, {FE_MUL, SL_X2}, {FE_STORE, SL_XT}, {FE_SQN, 4},     \
+      {FE_CONJ, 0}, {FE_MUL, SL_XT}, {FE_MUL, SL_X1}, {FE_MUL, SL_X0}
+// a^x = conj(a^|x|)  (x < 0)
+#define CESS_FE_CYCEXP(s) CESS_FE_CYCEXP_ABS(s), {FE_CONJ, 0}
 
-// easy part: m = f^((p^6 - 1)(p^2 + 1)); hard part as in pairing.hpp
-// final_exponentiation (t2 = m).  SL_T0 doubles as scratch in the easy part.
-#define CESS_FE_BODY                                                                                              \
+// easy part: m = f^((p^6 - 1)(p^2 + 1)), left in the accumulator and in SL_M.
+// SL_T0 doubles as scratch.
+#define CESS_FE_EASY                                                                                              \
   {FE_LOAD, SL_F}, {FE_CONJ, 0}, {FE_STORE, SL_T0}, {FE_LOAD, SL_F}, {FE_INV, 0}, {FE_MUL, SL_T0},                 \
-      {FE_STORE, SL_T0}, {FE_FROB, 2}, {FE_MUL, SL_T0}, {FE_STORE, SL_M},                                          \
+      {FE_STORE, SL_T0}, {FE_FROB, 2}, {FE_MUL, SL_T0}, {FE_STORE, SL_M}
+
+// Gt-output form: hard part as in pairing.hpp final_exponentiation (t2 = m),
+// the reference crate's formula line by line, so that the Gt bytes compare
+// with the oracle's.
+#define CESS_FE_BODY                                                                                              \
+  CESS_FE_EASY,                                                                                                    \
       /* t1 = conj(cycsq(m)) */ {FE_SQN, 1}, {FE_CONJ, 0}, {FE_STORE, SL_T1},                                     \
       /* t3 = m^x */ CESS_FE_CYCEXP(SL_M), {FE_STORE, SL_T3},                                                      \
       /* t4 = cycsq(t3) */ {FE_SQN, 1}, {FE_STORE, SL_T4},                                                          \
@@ -583,10 +598,36 @@ enum FeSlot : uint8_t { SL_F = 0, SL_M, SL_T0, SL_T1, SL_T3, SL_T4, SL_T5, SL_T6
       /* t3 = frob2(t3 * t0) * t1 * t6 * t4 */ {FE_LOAD, SL_T3}, {FE_MUL, SL_T0}, {FE_FROB, 2}, {FE_MUL, SL_T1},  \
       {FE_MUL, SL_T6}
 #define CESS_FE_PROGRAM CESS_FE_BODY, {FE_MUL, SL_T4}, {FE_END, 0}
-// Verdict-only form (no Gt output): the result t3 * t4 is 1 iff t3 equals
-// t4^-1 = conj(t4) (t4 is in the cyclotomic subgroup), so the last multiply
-// becomes a comparison (is_conj12 of the accumulator and slot SL_T4).
-#define CESS_FE_PROGRAM_VERIFY CESS_FE_BODY, {FE_END, 0}
+
+// Verdict-only form (no Gt output).  With h = (p^4 - p^2 + 1) / r the hard
+// exponent,
+//   3 h = (x - 1)^2 (x + p) (x^2 + p^2 - 1) + 3
+// (Hayashida-Hayasaka-Teruya, eprint 2020/875), and gcd(3, r) = 1: for m in
+// the cyclotomic subgroup m^(3h) = 1 exactly when m^h = 1, so the decision is
+// that of the Gt-output form.  With E(a) = a^x:
+//   t0 = E(m) conj(m)                       = m^(x - 1)
+//   t1 = E(t0) conj(t0)                     = m^((x - 1)^2)
+//   t2 = E(t1) frob1(t1)                    = t1^(x + p)
+//   t3 = E(E(t2)) frob2(t2) conj(t2)        = t2^(x^2 + p^2 - 1)
+//   m^(3h) = t3 m^3 = 1  iff  t3 m = conj(m^2):
+// the program ends with t3 m in the accumulator and m^2 (one Granger-Scott
+// squaring) in SL_T4, and the caller compares them with is_conj12 -- six
+// products outside the five powers (the Gt-output form has nine).  A product
+// by conj(a) right after a power drops the power's own conjugation:
+// E(a) conj(a) = conj(a^|x| a).
+// A Miller value f = 0 gives m = 0 and every later value 0, which the
+// comparison accepts (0 = conj(0)), as the previous program's comparison did;
+// records that passed the subgroup checks never reach the kernel with f = 0.
+#define CESS_FE_PROGRAM_VERIFY                                                                                    \
+  CESS_FE_EASY, /* m^2 */ {FE_SQN, 1}, {FE_STORE, SL_T4},                                                          \
+      /* t0 */ CESS_FE_CYCEXP_ABS(SL_M), {FE_MUL, SL_M}, {FE_CONJ, 0}, {FE_STORE, SL_T0},                          \
+      /* t1 */ CESS_FE_CYCEXP_ABS(SL_T0), {FE_MUL, SL_T0}, {FE_CONJ, 0}, {FE_STORE, SL_T1},                        \
+      /* frob1(t1) */ {FE_FROB, 1}, {FE_STORE, SL_T3},                                                             \
+      /* t2 */ CESS_FE_CYCEXP(SL_T1), {FE_MUL, SL_T3}, {FE_STORE, SL_T0},                                          \
+      /* frob2(t2) */ {FE_FROB, 2}, {FE_STORE, SL_T3},                                                             \
+      /* E(t2) */ CESS_FE_CYCEXP(SL_T0), {FE_STORE, SL_T1},                                                        \
+      /* t3 */ CESS_FE_CYCEXP_ABS(SL_T1), {FE_MUL, SL_T0}, {FE_CONJ, 0}, {FE_MUL, SL_T3},                          \
+      /* t3 m */ {FE_MUL, SL_M}, {FE_END, 0}
 
 // n cyclotomic squarings of acc (Granger-Scott formulas, as cyclotomic_square
 // in field.hpp): pair (z0, z1) updates itself; the square of (z2, z3) updates
@@ -744,23 +785,16 @@ CESS_HD fp2 cyc_z0(const fp2& z1, const fp2& z2, const fp2& z3, const fp2& z4, c
   return add(mul_nr(add(dbl(sqr(z1)), dot2(z2, z5, neg(mul3(z3)), z4))), fp2_one());
 }
 
-// FE_CHAIN: the powers a^(2^k), k = 16, 48, 57, 60, 62, 63, of the cyclotomic
-// element a (store `base`) into the stores X(0..5): compressed squarings, then
-// z1 of the compressed powers with ONE Fp2 inversion (Montgomery's
-// simultaneous inversion: numerators parked in the z1 words, prefix products
-// of the denominators in the z0 words; safegcd inversion), then z0.  A lane
-// whose denominator vanishes (z2 = z3 = 0, e.g. a = 1 from an identity pair)
-// redoes its chain with Granger-Scott squarings (divergent, rare).
-// CESS_CHAIN_TAIL (default 1): the compressed run stops at a^(2^57); only
-// a^(2^16), a^(2^48), a^(2^57) are decompressed, and a^(2^60), a^(2^62),
-// a^(2^63) follow by 3 + 2 + 1 Granger-Scott squarings -- six uncompressed
-// squarings for three decompressions (pair_fe.hpp pcyc_chain).
-#ifndef CESS_CHAIN_TAIL
-#define CESS_CHAIN_TAIL 1
-#endif
+// FE_CHAIN: the powers a^(2^k), k = 16, 48, 57, of the cyclotomic element a
+// (store `base`) into the stores X(0..2): compressed squarings, then z1 of the
+// compressed powers with ONE Fp2 inversion (Montgomery's simultaneous
+// inversion: numerators parked in the z1 words, prefix products of the
+// denominators in the z0 words; safegcd inversion), then z0.  A lane whose
+// denominator vanishes (z2 = z3 = 0, e.g. a = 1 from an identity pair) redoes
+// its chain with Granger-Scott squarings (divergent, rare).
 template <class B, class XFn, class P, class DG = NoDiag>
 CESS_HD void cyc_chain(const B& base, XFn&& X, const P& pk, DG* dg = nullptr) {
-  constexpr int ND = CESS_CHAIN_TAIL ? 3 : 6;   // decompressed powers
+  constexpr int ND = 3;   // decompressed powers
   {
     pk.st(0, base.ld(1));   // z4, z5 of the running power
     pk.st(1, base.ld(5));
@@ -768,7 +802,7 @@ CESS_HD void cyc_chain(const B& base, XFn&& X, const P& pk, DG* dg = nullptr) {
     int k = 0;
 #pragma unroll 1
     for (int j = 0; j < ND; j++) {
-      const int stop = j == 0 ? 16 : j == 1 ? 48 : j == 2 ? 57 : j == 3 ? 60 : j == 4 ? 62 : 63;
+      const int stop = j == 0 ? 16 : j == 1 ? 48 : 57;
       if (dg) dg->template mark<0>();
       kcyc_run(pk, z2, z3, stop - k);
       if (dg) dg->template mark<3>();   // compressed squarings
@@ -810,26 +844,15 @@ CESS_HD void cyc_chain(const B& base, XFn&& X, const P& pk, DG* dg = nullptr) {
     x.st(0, cyc_z0(z1, x.ld(3), x.ld(2), x.ld(1), x.ld(5)));
     CESS_MEMBAR();
   }
-  if (degen) {   // Granger-Scott squarings with X(5) as the running power
-    const auto w = X(5);
+  if (degen) {   // Granger-Scott squarings with X(2) as the running power
+    const auto w = X(2);
     copy12(w, base);
 #pragma unroll 1
-    for (int j = 0; j < 5; j++) {
-      const int run = j == 0 ? 16 : j == 1 ? 32 : j == 2 ? 9 : j == 3 ? 3 : 2;
-      cyc_square_run(w, pk, run);
-      copy12(X(j), w);
-    }
-    cyc_square_run(w, pk, 1);
-  }
-#if CESS_CHAIN_TAIL
-  else {   // X3..X5 from X2 = a^(2^57): 3, 2, 1 squarings
-#pragma unroll 1
-    for (int j = 3; j < 6; j++) {
-      copy12(X(j), X(j - 1));
-      cyc_square_run(X(j), pk, j == 3 ? 3 : j == 4 ? 2 : 1);
+    for (int j = 0; j < ND; j++) {
+      cyc_square_run(w, pk, j == 0 ? 16 : j == 1 ? 32 : 9);
+      if (j < ND - 1) copy12(X(j), w);
     }
   }
-#endif
   if (dg) dg->template mark<4>();   // decompression (and the rare fallback)
 }
 

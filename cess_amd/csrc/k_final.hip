@@ -2,9 +2,9 @@
 // k_final: final exponentiation -> code 0/5 + verdict bitmap (src/lib.rs:93-99, A13/A14)
 //
 // The exponentiation runs as a short program (bls/staged.hpp CESS_FE_PROGRAM)
-// over two ping-pong accumulators (HBM slots 8 and 9) and seven HBM slots
-// (uint4 SoA, stride = context capacity) for the cold Fp12 temporaries; the
-// Miller-loop output is slot SL_F.  Cyclotomic square runs hold the accumulator in
+// over two ping-pong accumulators (the last two HBM slots) and the slots
+// SL_M .. SL_TM (uint4 SoA, stride = context capacity) for the cold Fp12
+// temporaries; the Miller-loop output is slot SL_F.  Cyclotomic square runs hold the accumulator in
 // registers, with a third of it parked in LDS (two waves per SIMD).
 #include <hip/hip_runtime.h>
 #include "soa.hpp"
@@ -13,8 +13,10 @@ using namespace bls;
 using namespace cess;
 
 __constant__ uint8_t kFeProgram[][2] = {CESS_FE_PROGRAM};
-// verdict only (no Gt bytes requested): one Fp12 multiply less (staged.hpp)
+// verdict only (no Gt bytes requested): the shorter hard part, ending in a
+// comparison with conj(SL_T4) (staged.hpp)
 __constant__ uint8_t kFeProgramVerify[][2] = {CESS_FE_PROGRAM_VERIFY};
+static_assert(CESS_FE_SLOTS == SL_N + 1, "host slot allocation: SL_M .. SL_TM and two accumulators");
 
 // two waves per SIMD (one wave with 512 registers and no scratch measured
 // slower: 245 vs 212 ms per 1 M, profiles/r02g_sweep.txt)
@@ -67,6 +69,8 @@ __global__ CESS_LB_F12 void k_final(uint64_t n, uint8_t* __restrict__ code, uint
         const int which = final_exp_staged(acc0, acc1, gt_out ? kFeProgram : kFeProgramVerify, slot,
                                            LdsF12{park, wave_first_thread()}, dgp);
         const GlobF12W acc = which ? acc1 : acc0;
+        // verdict only: the program leaves t3 m in acc and m^2 in SL_T4; the
+        // result is 1 iff t3 m == conj(m^2) (staged.hpp CESS_FE_PROGRAM_VERIFY)
         if (!(gt_out ? is_one12(acc) : is_conj12(acc, slot(SL_T4)))) c = CODE_PAIRING;
         if (gt_out) {   // optional Gt bytes for parity tests (576 B per signature)
 #pragma unroll 1

@@ -36,6 +36,8 @@ __global__ __launch_bounds__(CESS_PAIR_THREADS, 2) void k_final2(uint64_t n, uin
       // f = 1 ((O, O) records) has f^e = 1 (k_final.hip)
       if (gt_out || !pis_one12(slot(SL_F))) {
         final_exp_pair(acc, gt_out ? kFeProgramPair : kFeProgramPairVerify, slot);
+        // verdict only: the program leaves t3 m in acc and m^2 in SL_T4; the
+        // result is 1 iff t3 m == conj(m^2) (staged.hpp CESS_FE_PROGRAM_VERIFY)
         if (!(gt_out ? pis_one12(acc) : pis_conj12(acc, slot(SL_T4)))) c = CODE_PAIRING;
         if (gt_out) {   // 576 B per signature: Fp 2k + h of tower order from lane h
 #pragma unroll 1

@@ -1,5 +1,8 @@
 """Count Fp multiplies/squares per signature per stage, from the device source
-compiled for the host (tests/hostemu/emu.cpp with -DCESS_COUNT_OPS).
+compiled for the host (tests/hostemu/emu.cpp with -DCESS_COUNT_OPS).  k_final
+is the verdict-only final-exponentiation program, the one the per-signature
+kernels run (tests/hostemu/fe_prog_emu.cpp); the Gt-output program's count is
+recorded beside it.
 Writes profiles/opcount.json (the algorithmic-work denominator of bench.py)."""
 import ctypes
 import json
@@ -13,16 +16,27 @@ lib_path = "/tmp/libemu_count.so"
 subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCESS_HOSTEMU", "-DCESS_COUNT_OPS", "-shared", "-fPIC",
                        os.path.join(ROOT, "tests", "hostemu", "emu.cpp"), "-o", lib_path])
 L = ctypes.CDLL(lib_path)
+fe_lib_path = "/tmp/libfe_prog_count.so"
+subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCESS_HOSTEMU", "-DCESS_COUNT_OPS", "-shared", "-fPIC",
+                       os.path.join(ROOT, "tests", "hostemu", "fe_prog_emu.cpp"), "-o", fe_lib_path])
+LF = ctypes.CDLL(fe_lib_path)
 vec = json.load(open(os.path.join(ROOT, "tests", "golden", "vectors.json")))
 stages = ["k_decode_sig", "k_decode_pk", "k_hash", "k_prepare", "k_miller", "k_final"]
-rows = []
+rows, gt_rows = [], []
 for c in vec["cases"]:
     if c["code"] != 0 or not c["name"].startswith("valid_len32"):
         continue
     out = (ctypes.c_uint64 * 12)()
     m = bytes.fromhex(c["msg"])
     L.emu_opcount(bytes.fromhex(c["sig"]), m, len(m), bytes.fromhex(c["pk"]), out)
-    rows.append([(out[2 * i] / 2, out[2 * i + 1]) for i in range(6)])   # mul in half units
+    row = [(out[2 * i] / 2, out[2 * i + 1]) for i in range(6)]   # mul in half units
+    fe = (ctypes.c_uint64 * 2)()
+    LF.emu_fe_opcount(bytes.fromhex(c["sig"]), m, len(m), bytes.fromhex(c["pk"]), 0, fe)
+    assert (fe[0] / 2, fe[1]) == row[5], (fe[0], fe[1], row[5])   # the Gt-output program, both ways
+    gt_rows.append(row[5])
+    LF.emu_fe_opcount(bytes.fromhex(c["sig"]), m, len(m), bytes.fromhex(c["pk"]), 1, fe)
+    row[5] = (fe[0] / 2, fe[1])
+    rows.append(row)
 avg = {st: {"mul": sum(r[i][0] for r in rows) / len(rows), "sqr": sum(r[i][1] for r in rows) / len(rows)}
        for i, st in enumerate(stages)}
 tot_m = sum(v["mul"] for v in avg.values())
@@ -35,6 +49,9 @@ res = {
     "algorithmic_mads_per_sig": (tot_m + tot_s) * 288,
     "issued_mads_per_sig": tot_m * 392 + tot_s * 301,
 }
+res["k_final_gt_program"] = {"mul": sum(r[0] for r in gt_rows) / len(gt_rows),
+                             "sqr": sum(r[1] for r in gt_rows) / len(gt_rows),
+                             "what": "the Gt-output final-exponentiation program (Gt entry points, RLC checks)"}
 # generator side: k_sign (PrivateKey::sign) over the golden keygen/sign records
 srows = []
 for g in vec["keygen_sign"]:
