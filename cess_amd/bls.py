@@ -55,9 +55,15 @@ EXPORTS = (
     # include/cess_rsa.h (RSA PKCS#1 v1.5 raw verify, cp_enclave_verify::verify_rsa)
     "cess_rsa_parse_key", "cess_rsa_keys_load", "cess_rsa_verify_batch", "cess_rsa_verify_batch_device",
     "cess_rsa_verify",
+    # hashed mode (RSASSA-PKCS1-v1_5 with SHA-256, on-GPU hashing) and the key policies
+    "cess_rsa_parse_key_policy", "cess_rsa_keys_load_policy", "cess_rsa_verify_sha256_batch",
+    "cess_rsa_verify_sha256_batch_device", "cess_rsa_verify_sha256",
 )
+# exported too, outside the cess_bls_ / cess_rsa_ name space that EXPORTS lists
+EXPORTS_OTHER = ("cess_sha256_batch",)
 RSA_E_UNSUPPORTED = -10
 RSA_KEY_SPKI, RSA_KEY_PKCS1 = 0, 1
+RSA_POLICY_RSA_CRATE, RSA_POLICY_RING_2048_8192 = 0, 1   # include/cess_rsa.h CESS_RSA_POLICY_*
 RSA_CODE_NAMES = {0: "OK", 1: "SIG_LEN", 2: "SIG_RANGE", 3: "MSG_LEN", 4: "MISMATCH", 5: "KEY"}
 
 # infrastructure status codes (include/cess_bls.h)
@@ -164,6 +170,16 @@ def load_library(path: str = LIB_PATH):
                                               _u64p]
         lib.cess_rsa_verify_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
         lib.cess_rsa_verify.argtypes = [vp, _u8p, sz, _u8p, sz, _u8p, sz, ctypes.POINTER(ctypes.c_int)]
+        if hasattr(lib, "cess_rsa_verify_sha256_batch"):   # (absent from older builds used in A/B runs)
+            lib.cess_rsa_parse_key_policy.argtypes = [_u8p, sz, ctypes.c_int, ctypes.c_int, _u8p, sz,
+                                                      ctypes.POINTER(ctypes.c_size_t), _u64p]
+            lib.cess_rsa_keys_load_policy.argtypes = [vp, sz, _u8p, _u64p, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_int)]
+            lib.cess_rsa_verify_sha256_batch.argtypes = lib.cess_rsa_verify_batch.argtypes
+            lib.cess_rsa_verify_sha256_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+            lib.cess_rsa_verify_sha256.argtypes = [vp, _u8p, sz, ctypes.c_int, _u8p, sz, _u8p, sz,
+                                                   ctypes.POINTER(ctypes.c_int)]
+            lib.cess_sha256_batch.argtypes = [vp, sz, _u8p, _u64p, _u8p]
         lib.cess_bls_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
                                              _u64p, ctypes.c_int, ctypes.c_int]
         lib.cess_bls_launch_records.argtypes = [vp]
@@ -531,12 +547,17 @@ class Context:
         return bool(ok.value)
 
     # --- RSA PKCS#1 v1.5 raw verify (include/cess_rsa.h) -------------------
-    def rsa_keys_load(self, ders: Sequence[bytes], fmt: int = RSA_KEY_SPKI) -> list:
-        """Load the RSA key table (DER keys); returns per-key status (0, E_BAD_KEY, RSA_E_UNSUPPORTED)."""
+    def rsa_keys_load(self, ders: Sequence[bytes], fmt: int = RSA_KEY_SPKI,
+                      policy: int = RSA_POLICY_RSA_CRATE) -> list:
+        """Load the RSA key table (DER keys) under a key policy (RSA_POLICY_*); returns per-key
+        status (0, E_BAD_KEY, RSA_E_UNSUPPORTED)."""
         k = len(ders)
         st = (ctypes.c_int * max(k, 1))()
-        self._chk(self._lib.cess_rsa_keys_load(self._h, k, _buf(b"".join(bytes(d) for d in ders)),
-                                               _offsets([len(d) for d in ders]), fmt, st))
+        data, offs = _buf(b"".join(bytes(d) for d in ders)), _offsets([len(d) for d in ders])
+        if policy == RSA_POLICY_RSA_CRATE:
+            self._chk(self._lib.cess_rsa_keys_load(self._h, k, data, offs, fmt, st))
+        else:
+            self._chk(self._lib.cess_rsa_keys_load_policy(self._h, k, data, offs, fmt, policy, st))
         return list(st)[:k]
 
     def rsa_verify_batch(self, key_idx: Sequence[int], msgs: Sequence[bytes], sigs: Sequence[bytes]) -> bytes:
@@ -562,6 +583,43 @@ class Context:
         self._chk(self._lib.cess_rsa_verify(self._h, _buf(key_der), len(key_der), _buf(msg), len(msg), _buf(sig),
                                             len(sig), ctypes.byref(ok)))
         return bool(ok.value)
+
+    # --- RSASSA-PKCS1-v1_5 with SHA-256, hashed on the GPU (include/cess_rsa.h) ---
+    def rsa_verify_sha256_batch(self, key_idx: Sequence[int], msgs: Sequence[bytes], sigs: Sequence[bytes],
+                                with_bitmap: bool = False):
+        """Hashed-mode codes of records (key key_idx[i] of the loaded table, message i of any
+        length, signature i); with_bitmap: (codes, bitmap words)."""
+        n = len(key_idx)
+        idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        bitmap = (ctypes.c_uint64 * max((n + 63) // 64, 1))()
+        self._chk(self._lib.cess_rsa_verify_sha256_batch(self._h, n, idx, _buf(b"".join(sigs)),
+                                                         _offsets([len(x) for x in sigs]), _buf(b"".join(msgs)),
+                                                         _offsets([len(m) for m in msgs]), codes, bitmap))
+        if with_bitmap:
+            return bytes(codes)[:n], list(bitmap)[: (n + 63) // 64]
+        return bytes(codes)[:n]
+
+    def rsa_verify_sha256_batch_device(self, n, d_key_idx, d_sigs, d_sig_offs, d_msgs, d_msg_offs, d_codes, stream=0):
+        self._chk(self._lib.cess_rsa_verify_sha256_batch_device(self._h, n, d_key_idx, d_sigs, d_sig_offs, d_msgs,
+                                                                d_msg_offs, d_codes, stream or None))
+
+    def verify_rsa_sha256(self, key_der: bytes, msg: bytes, sig: bytes, fmt: int = RSA_KEY_SPKI) -> bool:
+        """verify_signature(&RSA_PKCS1_2048_8192_SHA256, msg, sig) (enclave-verify/src/lib.rs:165-169)
+        under ring's key policy; raises BlsInfraError(E_BAD_KEY / RSA_E_UNSUPPORTED) for the key."""
+        ok = ctypes.c_int()
+        key_der, msg, sig = bytes(key_der), bytes(msg), bytes(sig)
+        self._chk(self._lib.cess_rsa_verify_sha256(self._h, _buf(key_der), len(key_der), fmt, _buf(msg), len(msg),
+                                                   _buf(sig), len(sig), ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def sha256_batch(self, msgs: Sequence[bytes]) -> list:
+        """SHA-256 of every message (the hashed mode's digest kernel alone)."""
+        n = len(msgs)
+        out = (ctypes.c_uint8 * (32 * max(n, 1)))()
+        self._chk(self._lib.cess_sha256_batch(self._h, n, _buf(b"".join(msgs)), _offsets([len(m) for m in msgs]), out))
+        raw = bytes(out)
+        return [raw[32 * i:32 * (i + 1)] for i in range(n)]
 
     # --- generator side -------------------------------------------------
     def public_keys_raw(self, sks: bytes) -> bytes:
@@ -634,13 +692,13 @@ def shard_range(n: int, nranks: int, rank: int) -> Tuple[int, int, int]:
     return b.value, e.value, w.value
 
 
-def rsa_parse_key(der: bytes, fmt: int = RSA_KEY_SPKI) -> Tuple[bytes, int]:
-    """(modulus big-endian, e) of a DER RSA public key (host-side parse)."""
+def rsa_parse_key(der: bytes, fmt: int = RSA_KEY_SPKI, policy: int = RSA_POLICY_RSA_CRATE) -> Tuple[bytes, int]:
+    """(modulus big-endian, e) of a DER RSA public key the policy accepts (host-side parse)."""
     lib = load_library()
     der = bytes(der)
-    out = (ctypes.c_uint8 * 512)()
+    out = (ctypes.c_uint8 * 1024)()
     ln, e = ctypes.c_size_t(), ctypes.c_uint64()
-    st = lib.cess_rsa_parse_key(_buf(der), len(der), fmt, out, 512, ctypes.byref(ln), ctypes.byref(e))
+    st = lib.cess_rsa_parse_key_policy(_buf(der), len(der), fmt, policy, out, 1024, ctypes.byref(ln), ctypes.byref(e))
     if st != 0:
         raise BlsInfraError(lib.cess_bls_status_string(st).decode(), st)
     return bytes(out)[: ln.value], e.value

@@ -29,6 +29,8 @@ __global__ void k_rsa_count(uint64_t, const uint32_t*, uint32_t, const RsaKeyDev
 __global__ void k_rsa_scan(uint32_t, const uint32_t*, uint32_t*, uint32_t*);
 __global__ void k_rsa_scatter(uint64_t, const uint32_t*, uint32_t, const RsaKeyDev*, const uint8_t*, const uint64_t*,
                               const uint64_t*, const uint32_t*, uint32_t*, uint32_t*, uint64_t);
+// hashed mode front end (k_rsa_digest.hip): T_i = DigestInfo || SHA-256(msg_i), or the digests alone
+__global__ void k_rsa_digest(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*);
 // key-uniform lists when the table has at most this many keys and the batch at
 // least this many records per key (padding each (class, key) segment to a
 // multiple of 64 then costs < 25 % idle lanes in the worst case)
@@ -77,7 +79,8 @@ bool der_uint(const Tlv& t, std::vector<uint8_t>& out) {
   return true;
 }
 
-bool parse_pkcs1(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t& e) {
+bool parse_pkcs1(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t& e,
+                 int policy = CESS_RSA_POLICY_RSA_CRATE) {
   Tlv seq, tn, te;
   if (!tlv(b, n, 0, seq) || seq.tag != 0x30 || seq.end != n) return false;
   if (!tlv(seq.v, seq.len, 0, tn) || !tlv(seq.v, seq.len, tn.end, te) || te.end != seq.len) return false;
@@ -86,6 +89,19 @@ bool parse_pkcs1(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t
   if (eb.size() > 8) return false;
   e = 0;
   for (uint8_t v : eb) e = (e << 8) | v;
+  if (policy == CESS_RSA_POLICY_RING_2048_8192) {
+    // ring's Key::from_modulus_and_exponent under RSA_PKCS1_2048_8192_SHA256
+    // (src/rsa/verification.rs:30-80, arithmetic/bigint.rs:251-263, 683-728):
+    // the modulus length rounded up to whole bytes is at least 2048 bits (so
+    // 2041..2047-bit moduli pass, as in ring) and the exact length at most
+    // 8192; n odd; e odd with 3 <= e <= 2^33 - 1
+    if (mod.empty()) return false;
+    size_t bits = 8 * mod.size();
+    for (uint8_t v = mod[0]; !(v & 0x80); v <<= 1) bits--;
+    if (8 * mod.size() < 2048 || bits > 8192) return false;
+    if (!(mod.back() & 1)) return false;
+    return (e & 1) && e >= 3 && e <= (1ull << 33) - 1;
+  }
   // rsa 0.8 key checks (RsaPublicKey::new -> check_public): n at most 4096
   // bits, 2 <= e <= 2^33 - 1.  Keys the crate accepts but this verifier cannot
   // represent (even or tiny moduli) are reported by kernel_can_verify, not here.
@@ -103,7 +119,8 @@ bool kernel_can_verify(const std::vector<uint8_t>& mod) {
 
 // *unsup: the AlgorithmIdentifier carries parameters other than NULL (the
 // crate's acceptance of those is unpinned here: reported as unsupported)
-bool parse_spki(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t& e, bool* unsup) {
+bool parse_spki(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t& e, bool* unsup,
+                int policy = CESS_RSA_POLICY_RSA_CRATE) {
   Tlv seq, alg, bits, oid, nul;
   if (!tlv(b, n, 0, seq) || seq.tag != 0x30 || seq.end != n) return false;
   if (!tlv(seq.v, seq.len, 0, alg) || alg.tag != 0x30) return false;
@@ -116,7 +133,7 @@ bool parse_spki(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t&
     if (nul.tag != 0x05 || nul.len != 0) *unsup = true;
   }
   if (bits.len < 1 || bits.v[0] != 0) return false;
-  return parse_pkcs1(bits.v + 1, bits.len - 1, mod, e);
+  return parse_pkcs1(bits.v + 1, bits.len - 1, mod, e, policy);
 }
 
 // limbs of the key's size class.  Every class must satisfy BOTH
@@ -203,6 +220,7 @@ struct RsaTable {
 struct RsaState {
   RsaTable user, single;
   DevBuf lists, counts, base, in_idx, in_sigs, in_soffs, in_msgs, in_moffs, out_codes;
+  DevBuf t, t_offs;   // hashed mode: T_i at stride 51 and its offsets (k_rsa_digest)
 };
 
 static RsaState& rsa_state(cess_bls_ctx* c) {
@@ -215,7 +233,7 @@ void cess_rsa_state_free(cess_bls_ctx* c) {
 }
 
 static int load_table(cess_bls_ctx* c, RsaTable& T, size_t k, const uint8_t* ders, const uint64_t* offs, int format,
-                      int* status_out) {
+                      int* status_out, int policy = CESS_RSA_POLICY_RSA_CRATE) {
   std::vector<RsaKeyDev> rows(std::max<size_t>(k, 1));
   std::vector<uint8_t> ok(std::max<size_t>(k, 1), 0);
   bool big = false;
@@ -227,7 +245,7 @@ static int load_table(cess_bls_ctx* c, RsaTable& T, size_t k, const uint8_t* der
     int st = CESS_BLS_OK;
     bool unsup = false;
     const bool parsed =
-        format == CESS_RSA_KEY_PKCS1 ? parse_pkcs1(d, len, mod, e) : parse_spki(d, len, mod, e, &unsup);
+        format == CESS_RSA_KEY_PKCS1 ? parse_pkcs1(d, len, mod, e, policy) : parse_spki(d, len, mod, e, &unsup, policy);
     if (!parsed) st = CESS_BLS_E_BAD_KEY;
     else if (unsup || !kernel_can_verify(mod)) st = CESS_RSA_E_UNSUPPORTED;
     int L = 0;
@@ -330,9 +348,40 @@ static int rsa_run(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, cons
   return CESS_BLS_OK;
 }
 
+// k_rsa_digest over device-resident messages, enqueued on s: `out` receives
+// 64 (n / 64 + 1) records of 51 (prefix) or 32 bytes, t_offs (prefix only)
+// n + 1 offsets
+static size_t digest_records(uint64_t n) { return 64 * (n / 64 + 1); }
+static int digest_run(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uint8_t* d_msgs, const uint64_t* d_moffs,
+                      uint8_t* out, bool prefix, uint64_t* t_offs) {
+  hipEvent_t a;
+  int r = prof_begin(c, s, ST_RSA_DIGEST, &a);
+  if (r) return r;
+  hipLaunchKernelGGL(k_rsa_digest, dim3((unsigned)(n / 64 + 1)), dim3(64), 0, s, n, d_msgs, d_moffs, out,
+                     prefix ? 1u : 0u, t_offs);
+  r = prof_end(c, s, ST_RSA_DIGEST, a);
+  if (r) return r;
+  HIPCHK(hipGetLastError());
+  return CESS_BLS_OK;
+}
+
+// hashed mode: T_i = DigestInfo || SHA-256(msg_i) into the context's buffer,
+// then the raw path over (T, t_offs) in place of (msgs, msg_offs)
+static int rsa_run_sha256(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, const uint32_t* d_idx,
+                          const uint8_t* d_sigs, const uint64_t* d_soffs, const uint8_t* d_msgs,
+                          const uint64_t* d_moffs, uint8_t* d_codes) {
+  if (n == 0) return CESS_BLS_OK;
+  if (n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
+  RsaState& S = rsa_state(c);
+  if (S.t.ensure(digest_records(n) * 51) | S.t_offs.ensure((n + 1) * 8)) return CESS_BLS_E_OOM;
+  int r = digest_run(c, s, n, d_msgs, d_moffs, S.t.as<uint8_t>(), true, S.t_offs.as<uint64_t>());
+  if (r) return r;
+  return rsa_run(c, T, s, n, d_idx, d_sigs, d_soffs, S.t.as<uint8_t>(), S.t_offs.as<uint64_t>(), d_codes);
+}
+
 static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
                     const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
-                    uint64_t* bitmap_out) {
+                    uint64_t* bitmap_out, bool sha256 = false) {
   if (n == 0) return CESS_BLS_OK;
   if (!key_idx || !soffs || !moffs) return CESS_BLS_E_INVALID_ARG;
   RsaState& S = rsa_state(c);
@@ -348,15 +397,16 @@ static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_
     mo[i] = moffs[i] - moffs[0];
   }
   if (S.in_idx.ensure(n * 4) | S.in_sigs.ensure(std::max<uint64_t>(sb, 1)) | S.in_soffs.ensure((n + 1) * 8) |
-      S.in_msgs.ensure(std::max<uint64_t>(mb, 1)) | S.in_moffs.ensure((n + 1) * 8) | S.out_codes.ensure(n))
+      S.in_msgs.ensure(mb + 4) /* k_rsa_digest fetches whole dwords (rsa_digest.hpp) */ | S.in_moffs.ensure((n + 1) * 8) | S.out_codes.ensure(n))
     return CESS_BLS_E_OOM;
   HIPCHK(hipMemcpyAsync(S.in_idx.p, key_idx, n * 4, hipMemcpyHostToDevice, s));
   if (sb) HIPCHK(hipMemcpyAsync(S.in_sigs.p, sigs + soffs[0], sb, hipMemcpyHostToDevice, s));
   if (mb) HIPCHK(hipMemcpyAsync(S.in_msgs.p, msgs + moffs[0], mb, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(S.in_soffs.p, so.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(S.in_moffs.p, mo.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  r = rsa_run(c, T, s, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(), S.in_soffs.as<uint64_t>(),
-              S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.out_codes.as<uint8_t>());
+  r = (sha256 ? rsa_run_sha256 : rsa_run)(c, T, s, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(),
+                                          S.in_soffs.as<uint64_t>(), S.in_msgs.as<uint8_t>(),
+                                          S.in_moffs.as<uint64_t>(), S.out_codes.as<uint8_t>());
   if (r) return r;
   r = collect_profile(c, s);
   if (r) return r;
@@ -390,18 +440,47 @@ extern "C" int cess_rsa_parse_key(const uint8_t* der, size_t len, int format, ui
   return CESS_BLS_OK;
 }
 
-extern "C" int cess_rsa_keys_load(cess_bls_ctx* c, size_t k, const uint8_t* ders, const uint64_t* der_offsets,
-                                  int format, int* key_status_out) {
-  ENTRY(c);
-  if ((k && (!ders || !der_offsets)) || k > 0xffffffffull) return CESS_BLS_E_INVALID_ARG;
+static bool policy_known(int policy) {
+  return policy == CESS_RSA_POLICY_RSA_CRATE || policy == CESS_RSA_POLICY_RING_2048_8192;
+}
+
+extern "C" int cess_rsa_parse_key_policy(const uint8_t* der, size_t len, int format, int policy, uint8_t* n_out,
+                                         size_t n_cap, size_t* n_len, uint64_t* e_out) {
+  if ((!der && len) || !n_len || !e_out || !policy_known(policy)) return CESS_BLS_E_INVALID_ARG;
   if (format != CESS_RSA_KEY_SPKI && format != CESS_RSA_KEY_PKCS1) return CESS_BLS_E_INVALID_ARG;
-  if (c->subs.empty()) return load_table(c, rsa_state(c).user, k, ders, der_offsets, format, key_status_out);
+  std::vector<uint8_t> mod;
+  uint64_t e = 0;
+  bool unsup = false;   // not reported here, as in cess_rsa_parse_key
+  const bool ok = format == CESS_RSA_KEY_PKCS1 ? parse_pkcs1(der, len, mod, e, policy)
+                                               : parse_spki(der, len, mod, e, &unsup, policy);
+  if (!ok) return CESS_BLS_E_BAD_KEY;
+  *n_len = mod.size();
+  *e_out = e;
+  if (n_out) {
+    if (n_cap < mod.size()) return CESS_BLS_E_INVALID_ARG;
+    memcpy(n_out, mod.data(), mod.size());
+  }
+  return CESS_BLS_OK;
+}
+
+extern "C" int cess_rsa_keys_load_policy(cess_bls_ctx* c, size_t k, const uint8_t* ders, const uint64_t* der_offsets,
+                                         int format, int policy, int* key_status_out) {
+  ENTRY(c);
+  if ((k && (!ders || !der_offsets)) || k > 0xffffffffull || !policy_known(policy)) return CESS_BLS_E_INVALID_ARG;
+  if (format != CESS_RSA_KEY_SPKI && format != CESS_RSA_KEY_PKCS1) return CESS_BLS_E_INVALID_ARG;
+  if (c->subs.empty())
+    return load_table(c, rsa_state(c).user, k, ders, der_offsets, format, key_status_out, policy);
   for (size_t d = 0; d < c->subs.size(); d++) {
     int r = load_table(c->subs[d], rsa_state(c->subs[d]).user, k, ders, der_offsets, format,
-                       d == 0 ? key_status_out : nullptr);
+                       d == 0 ? key_status_out : nullptr, policy);
     if (r) return r;
   }
   return CESS_BLS_OK;
+}
+
+extern "C" int cess_rsa_keys_load(cess_bls_ctx* c, size_t k, const uint8_t* ders, const uint64_t* der_offsets,
+                                  int format, int* key_status_out) {
+  return cess_rsa_keys_load_policy(c, k, ders, der_offsets, format, CESS_RSA_POLICY_RSA_CRATE, key_status_out);
 }
 
 int cess_multi_rsa(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
@@ -436,6 +515,99 @@ extern "C" int cess_rsa_verify_batch_device(cess_bls_ctx* c, size_t n, const uin
   r = collect_profile(c, s);   // no-op without CESS_BLS_F_PROFILE
   if (r) return r;
   return order_end(c, s);
+}
+
+// --- hashed mode: RSASSA-PKCS1-v1_5 with SHA-256 -----------------------------
+int cess_multi_rsa_sha256(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                          const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                          uint64_t* bitmap_out);
+
+int cess_rsa_sha256_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
+                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out) {
+  return rsa_host(s, rsa_state(s).user, n, key_idx, sigs, soffs, msgs, moffs, codes_out, bitmap_out, true);
+}
+
+extern "C" int cess_rsa_verify_sha256_batch(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                                            const uint64_t* sig_offsets, const uint8_t* msgs,
+                                            const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out) {
+  ENTRY(c);
+  if (!c->subs.empty())
+    return cess_multi_rsa_sha256(c, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out);
+  return rsa_host(c, rsa_state(c).user, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out,
+                  true);
+}
+
+extern "C" int cess_rsa_verify_sha256_batch_device(cess_bls_ctx* c, size_t n, const uint32_t* d_key_idx,
+                                                   const uint8_t* d_sigs, const uint64_t* d_sig_offsets,
+                                                   const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
+                                                   uint8_t* d_codes, void* stream) {
+  ENTRY(c);
+  if (!c->subs.empty() || (n && (!d_key_idx || !d_sig_offsets || !d_msg_offsets || !d_codes)))
+    return CESS_BLS_E_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  int r = order_begin(c, s);
+  if (r) return r;
+  r = rsa_run_sha256(c, rsa_state(c).user, s, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs, d_msg_offsets, d_codes);
+  if (r) return r;
+  r = collect_profile(c, s);   // no-op without CESS_BLS_F_PROFILE
+  if (r) return r;
+  return order_end(c, s);
+}
+
+extern "C" int cess_rsa_verify_sha256(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, int format,
+                                      const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len,
+                                      int* ok_out) {
+  ENTRY(c);
+  if (!ok_out || (!key_der && key_len) || (!msg && msg_len) || (!sig && sig_len)) return CESS_BLS_E_INVALID_ARG;
+  if (format != CESS_RSA_KEY_SPKI && format != CESS_RSA_KEY_PKCS1) return CESS_BLS_E_INVALID_ARG;
+  *ok_out = 0;
+  cess_bls_ctx* d = c->subs.empty() ? c : c->subs[0];
+  static const uint8_t zero = 0;
+  const uint64_t ko[2] = {0, key_len};
+  int st = CESS_BLS_OK;
+  RsaTable& T = rsa_state(d).single;
+  int r = load_table(d, T, 1, key_der ? key_der : &zero, ko, format, &st, CESS_RSA_POLICY_RING_2048_8192);
+  if (r) return r;
+  if (st) return st;   // ring rejects the key (BAD_KEY) or the GPU cannot verify it (UNSUPPORTED)
+  const uint32_t idx = 0;
+  const uint64_t so[2] = {0, sig_len}, mo[2] = {0, msg_len};
+  uint8_t code = 0xff;
+  r = rsa_host(d, T, 1, &idx, sig ? sig : &zero, so, msg ? msg : &zero, mo, &code, nullptr, true);
+  if (r) return r;
+  *ok_out = code == RSA_OK;
+  return CESS_BLS_OK;
+}
+
+extern "C" int cess_sha256_batch(cess_bls_ctx* c, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                 uint8_t* out32) {
+  ENTRY(c);
+  if (n == 0) return CESS_BLS_OK;
+  if (!msg_offsets || !out32 || n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
+  cess_bls_ctx* d = c->subs.empty() ? c : c->subs[0];
+  RsaState& S = rsa_state(d);
+  HIPCHK(hipSetDevice(d->device));
+  hipStream_t s = d->stream;
+  int r = order_begin(d, s);
+  if (r) return r;
+  const uint64_t mb = msg_offsets[n] - msg_offsets[0];
+  std::vector<uint64_t> mo(n + 1);
+  for (size_t i = 0; i <= n; i++) {
+    if (i && msg_offsets[i] < msg_offsets[i - 1]) return CESS_BLS_E_INVALID_ARG;
+    mo[i] = msg_offsets[i] - msg_offsets[0];
+  }
+  if (mb && !msgs) return CESS_BLS_E_INVALID_ARG;
+  if (S.in_msgs.ensure(mb + 4) | S.in_moffs.ensure((n + 1) * 8) | S.t.ensure(digest_records(n) * 32))
+    return CESS_BLS_E_OOM;
+  if (mb) HIPCHK(hipMemcpyAsync(S.in_msgs.p, msgs + msg_offsets[0], mb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(S.in_moffs.p, mo.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  r = digest_run(d, s, n, S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.t.as<uint8_t>(), false, nullptr);
+  if (r) return r;
+  r = collect_profile(d, s);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(out32, S.t.p, n * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return order_end(d, s);
 }
 
 extern "C" int cess_rsa_verify(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, const uint8_t* msg,

@@ -1,0 +1,152 @@
+// k_rsa_digest: SHA-256 of n independent, variable-length, arbitrarily aligned
+// messages -- the hashed RSA mode's front end (RSASSA-PKCS1-v1_5 with SHA-256,
+// ring's RSA_PKCS1_2048_8192_SHA256).  Record i gets T_i = DigestInfo prefix ||
+// H(msg_i) (51 bytes, stride 51) and t_offs[i] = 51 i, which the unchanged raw
+// RSA path (host_rsa.cpp rsa_run) then takes as its (msgs, msg_offs); with
+// prefix = 0 the 32-byte digests alone (cess_sha256_batch).
+//
+// Layout: one wave per workgroup, one lane per message.  A lane walking its
+// own message with byte loads would make every wave load touch 64 cache lines,
+// so the wave stages cooperatively instead.  Per round it copies the next
+// kRoundBlocks 64-byte blocks of each of its 64 messages into LDS: the 64
+// lanes fetch message m's 64 aligned dwords that cover those 256 bytes with
+// one coalesced load and store them, as fetched, to row m (the message's
+// start, length and shift are scalars of that iteration).  Each lane then
+// reads its own row and turns the raw dwords into big-endian stream words:
+// a byte funnel shift over neighbouring dwords removes the misalignment (the
+// 65th dword it needs at the end of a round comes from one per-lane load), and
+// the blocks that hold the message's end get the SHA padding
+// (rsa_digest.hpp).  It compresses kRoundBlocks blocks per round; state and
+// schedule stay in VGPRs.
+//
+// Chunk size.  State, schedule, a block's raw dwords and a batch of staged
+// loads take about 115 VGPRs, so registers allow 4 waves per SIMD; LDS
+// decides.  A row is 16 kRoundBlocks + 1 dwords: the odd stride puts the 32 lanes of a ds_read_b32 group on 32 different banks when they
+// read word j of their rows (stride 65 = 1 mod 32), and the staging stores of
+// one row are consecutive.  kRoundBlocks = 4 makes one wave load cover one
+// message's 256 contiguous bytes (a full-width coalesced access, message
+// parameters in SGPRs) at 64 x 65 x 4 = 16,640 B per wave: 9 waves per CU of
+// 160 KiB, two per SIMD and one over, so a staging wave (latency-bound) has a
+// compressing wave (VALU-bound) beside it.  Two blocks would double the
+// occupancy but halve the contiguous run and need per-lane message
+// parameters; eight would leave one wave per SIMD.
+//
+// Lanes whose message has ended idle until the longest message of the wave is
+// done: the wave's time is that of its longest message.  A batch with one very
+// long record keeps that record's wave (and only it) busy for
+// len / 64 compressions on a single lane; sorting or splitting such batches is
+// the caller's business.
+//
+// Loads stay inside the dwords that hold message bytes (rsa_digest.hpp); lanes
+// with nothing to fetch read the first dword of msg_offs instead, so the loads
+// are unconditional and a batch of them is in flight at once.  A record whose
+// offsets are not ordered or exceed msg_offs[n] is hashed as empty.
+#include <hip/hip_runtime.h>
+
+#include "rsa_digest.hpp"
+
+namespace {
+
+constexpr int kRoundBlocks = 4;                  // 64-byte blocks per message and round
+constexpr int kRoundWords = 16 * kRoundBlocks;   // = the wave's 64 lanes: one stream word per lane
+constexpr int kRowStride = kRoundWords + 1;      // dwords
+constexpr int kBatch = 8;                        // messages whose loads are issued together
+static_assert(kRoundWords == 64, "one stream word per lane");
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void k_rsa_digest(uint64_t n, const uint8_t* __restrict__ msgs,
+                                                   const uint64_t* __restrict__ msg_offs, uint8_t* __restrict__ out,
+                                                   uint32_t prefix, uint64_t* __restrict__ t_offs) {
+  using namespace rsa_digest;
+  __shared__ uint32_t rows[64 * kRowStride];
+  const uint32_t lane = threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * 64 + lane;
+  uint64_t start = 0, len = 0;
+  if (i < n) {
+    const uint64_t total = msg_offs[n], b = msg_offs[i], e = msg_offs[i + 1];
+    if (b <= e && e <= total) {
+      start = b;
+      len = e - b;
+    }
+  }
+  if (t_offs && i <= n) t_offs[i] = (uint64_t)kTLen * i;
+  const uint64_t nblk = i < n ? padded_len(len) / 64 : 0;
+  unsigned long long mx = nblk;
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const unsigned long long o = __shfl_xor(mx, off);
+    mx = o > mx ? o : mx;
+  }
+  const uint32_t* safe = reinterpret_cast<const uint32_t*>(msg_offs);
+  uint32_t st[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) st[j] = bls::SHA_IV[j];
+
+  const uint32_t sh = ((uint32_t)(uintptr_t)msgs + (uint32_t)start) & 3u;   // this lane's message
+#pragma unroll 1
+  for (uint64_t blk0 = 0; blk0 < mx; blk0 += kRoundBlocks) {
+    const uint64_t pos0 = blk0 * 64;
+    const uint32_t avail = window_avail(len, pos0);   // this lane's message
+    // raw dword 64 of the lane's own window (the funnel shift of the round's
+    // last word needs it): one per-lane load per round, in flight during staging
+    const uint32_t carry =
+        *(dword_needed(64, sh, avail) ? reinterpret_cast<const uint32_t*>(msgs + start + pos0 - sh) + 64 : safe);
+#pragma unroll 1
+    for (int m0 = 0; m0 < 64; m0 += kBatch) {
+      uint32_t raw[kBatch];
+      bool any = false;
+#pragma unroll
+      for (int u = 0; u < kBatch; u++) {   // message m0 + u: parameters in SGPRs, lane j fetches raw dword j
+        const uint32_t m_avail = window_avail(readlane64(len, m0 + u), pos0);
+        const uint8_t* a0 = msgs + readlane64(start, m0 + u) + pos0;
+        const uint32_t m_sh = (uint32_t)(uintptr_t)a0 & 3u;
+        any = any | (m_avail != 0);
+        raw[u] = *(dword_needed(lane, m_sh, m_avail) ? reinterpret_cast<const uint32_t*>(a0 - m_sh) + lane : safe);
+      }
+      if (!any) continue;   // (wave-uniform) no message bytes of these messages in this round
+#pragma unroll
+      for (int u = 0; u < kBatch; u++) rows[(m0 + u) * kRowStride + lane] = raw[u];
+    }
+    __syncthreads();   // one wave: orders the staging stores before the row reads
+#pragma unroll 1
+    for (int b = 0; b < kRoundBlocks; b++) {
+      if (blk0 + b < nblk) {
+        const uint32_t* row = rows + lane * kRowStride + 16 * b;
+        uint32_t r[17], blk[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) r[j] = row[j];
+        r[16] = b == kRoundBlocks - 1 ? carry : row[16];
+        if (64u * b + 64u <= avail) {   // the block lies inside the message: shift and swap only
+#pragma unroll
+          for (int j = 0; j < 16; j++)
+            blk[j] = __builtin_bswap32((uint32_t)((((uint64_t)r[j + 1] << 32) | r[j]) >> (8 * sh)));
+        } else {                        // the message's last bytes and the padding
+#pragma unroll
+          for (int j = 0; j < 16; j++) blk[j] = stream_word(r[j], r[j + 1], sh, avail, 64 * b + 4 * j, len, pos0);
+        }
+        bls::sha256_compress(st, blk);
+      }
+    }
+    __syncthreads();
+  }
+
+  // 64 records of rec bytes, assembled in LDS and written as consecutive dwords
+  const uint32_t rec = prefix ? kTLen : 32;
+  uint8_t* row = reinterpret_cast<uint8_t*>(rows) + rec * lane;
+  if (prefix) {
+#pragma unroll
+    for (int j = 0; j < kPrefixLen; j++) row[j] = kPrefix[j];
+    row += kPrefixLen;
+  }
+#pragma unroll
+  for (int j = 0; j < 32; j++) row[j] = (uint8_t)(st[j >> 2] >> (24 - 8 * (j & 3)));
+  __syncthreads();
+  uint32_t* o32 = reinterpret_cast<uint32_t*>(out + (uint64_t)blockIdx.x * 64 * rec);
+  for (uint32_t d = lane; d < 16 * rec; d += 64) o32[d] = rows[d];
+}

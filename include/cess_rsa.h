@@ -84,6 +84,71 @@ int cess_rsa_verify_batch_device(cess_bls_ctx* ctx, size_t n, const uint32_t* d_
 int cess_rsa_verify(cess_bls_ctx* ctx, const uint8_t* key_der, size_t key_len, const uint8_t* msg, size_t msg_len,
                     const uint8_t* sig, size_t sig_len, int* ok_out);
 
+/* ---------------------------------------------------------------------------
+ * Hashed mode: RSASSA-PKCS1-v1_5 with SHA-256 of a variable-length message,
+ * hashed on the GPU (k_rsa_digest).  Replaces the signature check of
+ * verify_miner_cert (reference primitives/enclave-verify/src/lib.rs:165-169):
+ *     sig_cert.verify_signature(&webpki::RSA_PKCS1_2048_8192_SHA256,
+ *                               report_json_raw, ias_sig)
+ * Record i passes iff sig_i^e mod n = 00 01 ff..ff 00 || T_i with
+ * T_i = DigestInfo(SHA-256) || SHA-256(msg_i) (51 bytes); everything after the
+ * hashing is the raw path above, over T_i in place of the message.
+ *
+ * Key policy.  Which keys load is chosen per table:
+ *   CESS_RSA_POLICY_RSA_CRATE       the rsa crate's checks (the raw mode's)
+ *   CESS_RSA_POLICY_RING_2048_8192  ring's under RSA_PKCS1_2048_8192_SHA256:
+ *     well-formed DER; the modulus length rounded up to whole bytes at least
+ *     2048 bits and the exact length at most 8192 bits (ring rounds up, so a
+ *     2041-bit modulus passes and a 2040-bit one does not); n odd; e odd;
+ *     3 <= e <= 2^33 - 1.  A key that fails any of these is
+ *     CESS_BLS_E_BAD_KEY.  A key that passes but is longer than 4096 bits is
+ *     CESS_RSA_E_UNSUPPORTED: the caller's CPU path decides.
+ * The policy governs key acceptance only: either verify mode runs over
+ * whatever table is loaded.
+ * ------------------------------------------------------------------------- */
+#define CESS_RSA_POLICY_RSA_CRATE 0
+#define CESS_RSA_POLICY_RING_2048_8192 1
+
+/* cess_rsa_parse_key under `policy`: whether that policy accepts the key
+ * (moduli up to 8192 bits = 1024 bytes under the ring policy). */
+int cess_rsa_parse_key_policy(const uint8_t* der, size_t len, int format, int policy, uint8_t* n_out, size_t n_cap,
+                              size_t* n_len, uint64_t* e_out);
+
+/* cess_rsa_keys_load under `policy` (policy 0: identical to cess_rsa_keys_load). */
+int cess_rsa_keys_load_policy(cess_bls_ctx* ctx, size_t k, const uint8_t* ders, const uint64_t* der_offsets,
+                              int format, int policy, int* key_status_out);
+
+/* Hashed verification over a batch; arguments as cess_rsa_verify_batch, msgs
+ * of any length and alignment.  Codes are cess_rsa_code; CESS_RSA_MSG_LEN now
+ * means k < 62 (no room for T), which a ring-policy table never produces.
+ * Host buffers; multi-device contexts shard the batch by index. */
+int cess_rsa_verify_sha256_batch(cess_bls_ctx* ctx, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                                 const uint64_t* sig_offsets, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                 uint8_t* codes_out, uint64_t* bitmap_out);
+
+/* Device-resident form: pointers and stream as cess_rsa_verify_batch_device.
+ * d_msg_offsets must be non-decreasing (a record whose range is not ordered
+ * or ends past d_msg_offsets[n] is hashed as the empty message).  The kernel
+ * fetches message bytes as whole aligned dwords, and only dwords that hold a
+ * message byte: it may read up to 3 bytes before d_msgs (if d_msgs is not
+ * 4-byte aligned) and up to 3 bytes past d_msgs + d_msg_offsets[n], never
+ * beyond the aligned dword of the first / last byte, so any device allocation
+ * that holds the messages is large enough. */
+int cess_rsa_verify_sha256_batch_device(cess_bls_ctx* ctx, size_t n, const uint32_t* d_key_idx, const uint8_t* d_sigs,
+                                        const uint64_t* d_sig_offsets, const uint8_t* d_msgs,
+                                        const uint64_t* d_msg_offsets, uint8_t* d_codes, void* stream);
+
+/* verify_signature(&RSA_PKCS1_2048_8192_SHA256, msg, sig) drop-in for one
+ * record: ring policy, key in `format`.  CESS_BLS_E_BAD_KEY where ring rejects
+ * the key, CESS_RSA_E_UNSUPPORTED where the GPU cannot verify it; else
+ * *ok_out = the verdict. */
+int cess_rsa_verify_sha256(cess_bls_ctx* ctx, const uint8_t* key_der, size_t key_len, int format, const uint8_t* msg,
+                           size_t msg_len, const uint8_t* sig, size_t sig_len, int* ok_out);
+
+/* SHA-256 of n messages (host buffers) -> out32 (32 n bytes): the hashed
+ * mode's digest kernel alone, exposed for tests. */
+int cess_sha256_batch(cess_bls_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets, uint8_t* out32);
+
 #ifdef __cplusplus
 }
 #endif

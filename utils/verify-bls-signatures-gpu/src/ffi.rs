@@ -189,8 +189,29 @@ extern "C" {
     pub fn cess_rsa_verify_batch_device(ctx: *mut cess_bls_ctx, n: usize, d_key_idx: *const u32, d_sigs: *const u8,
                                         d_sig_offsets: *const u64, d_msgs: *const u8, d_msg_offsets: *const u64,
                                         d_codes: *mut u8, stream: *mut c_void) -> c_int;
+
+    // hashed mode: verify_signature(&webpki::RSA_PKCS1_2048_8192_SHA256, ..) of verify_miner_cert
+    // (primitives/enclave-verify/src/lib.rs:165-169), SHA-256 on the GPU; key policies
+    pub fn cess_rsa_parse_key_policy(der: *const u8, len: usize, format: c_int, policy: c_int, n_out: *mut u8,
+                                     n_cap: usize, n_len: *mut usize, e_out: *mut u64) -> c_int;
+    pub fn cess_rsa_keys_load_policy(ctx: *mut cess_bls_ctx, k: usize, ders: *const u8, der_offsets: *const u64,
+                                     format: c_int, policy: c_int, key_status_out: *mut c_int) -> c_int;
+    pub fn cess_rsa_verify_sha256_batch(ctx: *mut cess_bls_ctx, n: usize, key_idx: *const u32, sigs: *const u8,
+                                        sig_offsets: *const u64, msgs: *const u8, msg_offsets: *const u64,
+                                        codes_out: *mut u8, bitmap_out: *mut u64) -> c_int;
+    pub fn cess_rsa_verify_sha256_batch_device(ctx: *mut cess_bls_ctx, n: usize, d_key_idx: *const u32,
+                                               d_sigs: *const u8, d_sig_offsets: *const u64, d_msgs: *const u8,
+                                               d_msg_offsets: *const u64, d_codes: *mut u8,
+                                               stream: *mut c_void) -> c_int;
+    pub fn cess_rsa_verify_sha256(ctx: *mut cess_bls_ctx, key_der: *const u8, key_len: usize, format: c_int,
+                                  msg: *const u8, msg_len: usize, sig: *const u8, sig_len: usize,
+                                  ok_out: *mut c_int) -> c_int;
+    pub fn cess_sha256_batch(ctx: *mut cess_bls_ctx, n: usize, msgs: *const u8, msg_offsets: *const u64,
+                             out32: *mut u8) -> c_int;
 }
 
+pub const CESS_RSA_POLICY_RSA_CRATE: c_int = 0;
+pub const CESS_RSA_POLICY_RING_2048_8192: c_int = 1;
 pub const CESS_RSA_E_UNSUPPORTED: c_int = -10;
 pub const CESS_RSA_KEY_SPKI: c_int = 0;
 pub const CESS_RSA_KEY_PKCS1: c_int = 1;
