@@ -73,7 +73,6 @@ int same_on_all_ranks(Transport& t, uint64_t v, bool* same);
 double comm_now_ms();
 double comm_timeout_ms();
 
-// shard of a batch for rank r of R (whole bitmap words, equal word count per rank; host.cpp)
-void shard_of(uint64_t n, int nranks, int rank, uint64_t* begin, uint64_t* end, uint64_t* words_per_rank);
-
 }  // namespace cess_host
+
+#include "host_pure.hpp"   // shard_of

@@ -60,20 +60,12 @@ int order_end(cess_bls_ctx* c, hipStream_t s) {
   return CESS_BLS_OK;
 }
 
-void bitmap_from_codes(const uint8_t* codes, uint64_t n, uint64_t* words) {
-  for (uint64_t w = 0; w < (n + 63) / 64; w++) words[w] = 0;
-  for (uint64_t i = 0; i < n; i++)
-    if (codes[i] == CODE_OK) words[i >> 6] |= 1ull << (i & 63);
-}
-
-void shard_of(uint64_t n, int nranks, int rank, uint64_t* begin, uint64_t* end, uint64_t* wpr) {
-  const uint64_t words = (n + 63) / 64;
-  const uint64_t per = nranks > 0 ? (words + nranks - 1) / nranks : 0;
-  const uint64_t b = std::min<uint64_t>(n, (uint64_t)rank * per * 64);
-  const uint64_t e = std::min<uint64_t>(n, ((uint64_t)rank + 1) * per * 64);
-  if (begin) *begin = b;
-  if (end) *end = e;
-  if (wpr) *wpr = per;
+int upload_msgs(hipStream_t s, const uint8_t* msgs, uint64_t first, uint64_t bytes,
+                const std::vector<uint64_t>& rebased, DevBuf& d_msgs, DevBuf& d_offs, uint64_t slack) {
+  if (d_msgs.ensure(std::max<uint64_t>(bytes + slack, 1)) | d_offs.ensure(rebased.size() * 8)) return CESS_BLS_E_OOM;
+  if (bytes) HIPCHK(hipMemcpyAsync(d_msgs.p, msgs + first, bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_offs.p, rebased.data(), rebased.size() * 8, hipMemcpyHostToDevice, s));
+  return CESS_BLS_OK;
 }
 
 }  // namespace cess_host
@@ -86,11 +78,7 @@ static int alloc_stage(cess_bls_ctx* c) {
   r |= c->bitmap.ensure((n / 64 + 1) * 8);
   r |= c->fval.ensure(q * CESS_W_FP12 * 4);
   r |= c->fe_slots.ensure(q * CESS_W_FP12 * 4 * CESS_FE_SLOTS);
-  for (int k = 0; k < (q < n ? 2 : 1); k++) {
-    r |= c->slot[k].inf.ensure(q);
-    r |= c->slot[k].sig_aff.ensure(q * CESS_W_G1 * 4);
-    r |= c->slot[k].h_aff.ensure(q * CESS_W_G1 * 4);
-  }
+  for (int k = 0; k < (q < n ? 2 : 1); k++) r |= c->slot[k].ensure(q, false);
   return r ? CESS_BLS_E_OOM : CESS_BLS_OK;
 }
 
@@ -123,53 +111,6 @@ static uint64_t small_records() {
   if (const char* e = getenv("CESS_BLS_SMALL_BATCH")) v = strtoull(e, nullptr, 10);
   return v;
 }
-
-// The Miller loop kernel: k_miller2 (default: a lane pair per signature,
-// 256-thread blocks of 128 signatures, two waves per SIMD; bls/pair.hpp) or
-// k_miller (one lane per signature, one wave per SIMD), env CESS_BLS_MILLER =
-// lane.  Both take the same arguments and write the same fval rows; k_miller2
-// runs config[1]'s Miller loop in 129.8-130.0 ms per 1 M against 149.5-149.7
-// (same box, profiles/round6_c_sweep_miller_pair.txt).
-typedef void (*MillerKernel)(uint64_t, const uint8_t*, const uint8_t*, const uint32_t*, const uint32_t*,
-                             const uint32_t*, const uint4*, uint4*, uint4*, uint64_t, const uint32_t*, uint64_t,
-                             const uint8_t*);
-static bool miller_pair() {
-  static const bool v = [] {
-    const char* e = getenv("CESS_BLS_MILLER");
-    return !(e && strcmp(e, "lane") == 0);
-  }();
-  return v;
-}
-static MillerKernel miller_kernel() { return miller_pair() ? k_miller2 : k_miller; }
-// the lane-pair kernels: blocks of CESS_PAIR_THREADS / 2 signatures
-constexpr uint64_t kPairSigs = CESS_PAIR_THREADS / 2;
-// (covering whole 64-record bitmap words: k_final2 writes 32-bit halves, one per
-// wave of 32 signatures, so both waves of a word must exist)
-static unsigned pair_grid(uint64_t m) {
-  const uint64_t m64 = (m + 63) & ~63ull;
-  return (unsigned)((m64 + kPairSigs - 1) / kPairSigs);
-}
-static dim3 miller_grid(uint64_t m) { return dim3(miller_pair() ? pair_grid(m) : grid_for(m)); }
-static dim3 miller_block() { return dim3(miller_pair() ? CESS_PAIR_THREADS : kBlock); }
-
-// The final-exponentiation kernel: k_final2 (default: a lane pair per
-// signature, the accumulator in LDS; bls/pair_fe.hpp) or k_final (one lane per
-// signature, accumulators in HBM), env CESS_BLS_FINAL = lane.  Same arguments
-// and outputs; k_final2 137.4-138.2 against 142.1 ms per 1 M on one box, ~99
-// against ~332 KB/sig counted traffic (profiles/round6_e_sweep_final_pair.txt).
-typedef void (*FinalKernel)(uint64_t, uint8_t*, uint4*, uint4*, uint64_t*, uint8_t*, uint64_t);
-static bool final_pair() {
-  static const bool v = [] {
-    const char* e = getenv("CESS_BLS_FINAL");
-    return !(e && strcmp(e, "lane") == 0);
-  }();
-  return v;
-}
-static FinalKernel final_kernel() { return final_pair() ? k_final2 : k_final; }
-static dim3 final_grid(uint64_t m) { return dim3(final_pair() ? pair_grid(m) : grid_for(m)); }
-static dim3 final_block() { return dim3(final_pair() ? CESS_PAIR_THREADS : kBlock); }
-
-int cess_multi_create(const cess_bls_config* cfg, int ndev, cess_bls_ctx* c);   // host_multi.cpp
 
 extern "C" int cess_bls_ctx_create(const cess_bls_config* cfg, cess_bls_ctx** out) {
   if (!out) return CESS_BLS_E_INVALID_ARG;
@@ -295,16 +236,6 @@ int cess_host::prof_end(cess_bls_ctx* c, hipStream_t s, int stage, hipEvent_t a)
   return CESS_BLS_OK;
 }
 
-#define LAUNCH(stage, strm, ...)                        \
-  do {                                                  \
-    hipEvent_t pa_;                                     \
-    int pr_ = prof_begin(c, strm, stage, &pa_);         \
-    if (pr_) return pr_;                                \
-    hipLaunchKernelGGL(__VA_ARGS__);                    \
-    pr_ = prof_end(c, strm, stage, pa_);                \
-    if (pr_) return pr_;                                \
-  } while (0)
-
 // The pipeline over one chunk of n <= cap records, in parts of <= qcap.
 // light(S, q, off, m, strm) enqueues the part's decode/hash(/prepare) kernels
 // into stage slot S on strm; heavy(S, q, off, m) its Miller loop and final
@@ -342,13 +273,9 @@ static int pipeline(cess_bls_ctx* c, hipStream_t s, uint64_t n, Light&& light, H
 int cess_host::run_chunk(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uint8_t* sigs, const uint8_t* pks,
                          const uint8_t* msgs, const uint64_t* offs, const uint8_t* pre, uint8_t* codes,
                          uint64_t* bitmap, uint8_t* gt) {
-  // per-record key buffers (19.6 KB of line coefficients per signature) are
-  // allocated on first use: keyed batches never touch them
+  // the per-record key buffers are allocated on first use
   for (int k = 0; k < (n > c->qcap ? 2 : 1); k++)
-    if (c->slot[k].inf.ensure(c->qcap) | c->slot[k].sig_aff.ensure(c->qcap * CESS_W_G1 * 4) |
-        c->slot[k].h_aff.ensure(c->qcap * CESS_W_G1 * 4) | c->slot[k].pk_aff.ensure(c->qcap * CESS_W_G2 * 4) |
-        c->slot[k].coeffs.ensure(c->qcap * (uint64_t)CESS_W_COEFFS * 4))
-      return CESS_BLS_E_OOM;
+    if (c->slot[k].ensure(c->qcap, true)) return CESS_BLS_E_OOM;
   const uint32_t strict = (c->flags & CESS_BLS_F_STRICT_IDENTITY) ? 1u : 0u;
   if (n <= c->small) {
     // small batch: decode + hash one lane per record, then one wave per record
@@ -402,7 +329,6 @@ int cess_host::run_chunk(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uint8
     return CESS_BLS_OK;
   };
   auto heavy = [&](StageSlot& S, uint64_t q, uint64_t off, uint64_t m) -> int {
-    const unsigned g = grid_for(m);
     LAUNCH(ST_MILLER, s, miller_kernel(), miller_grid(m), miller_block(), 0, s, m, (const uint8_t*)(codes + off),
            (const uint8_t*)S.inf.as<uint8_t>(), (const uint32_t*)S.sig_aff.as<uint32_t>(),
            (const uint32_t*)S.h_aff.as<uint32_t>(), (const uint32_t*)c->neg_g2.as<uint32_t>(),
@@ -417,8 +343,8 @@ int cess_host::run_chunk(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uint8
   return pipeline(c, s, n, light, heavy);
 }
 
-int cess_host::collect_profile(cess_bls_ctx* c, hipStream_t s) {
-  if (!(c->flags & CESS_BLS_F_PROFILE)) return CESS_BLS_OK;
+int cess_host::call_end(cess_bls_ctx* c, hipStream_t s) {
+  if (!(c->flags & CESS_BLS_F_PROFILE)) return order_end(c, s);
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipStreamSynchronize(c->stream2));
   HIPCHK(hipStreamSynchronize(c->stream3));
@@ -430,62 +356,6 @@ int cess_host::collect_profile(cess_bls_ctx* c, hipStream_t s) {
   }
   c->prof.clear();
   c->evused = 0;
-  return CESS_BLS_OK;
-}
-
-// Host-buffer batch over fixed-stride inputs (pre: optional host pre-flags).
-// msg offsets are absolute into msgs; each chunk is rebased.
-int cess_host::verify_host(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
-                           const uint64_t* offs, const uint8_t* pre, uint8_t* codes_out, uint64_t* bitmap_out,
-                           uint8_t* gt_out) {
-  if (n == 0) return CESS_BLS_OK;
-  if (!sigs || !pks || !offs || (!msgs && offs[n] != offs[0])) return CESS_BLS_E_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  int r = order_begin(c, s);
-  if (r) return r;
-  std::vector<uint64_t> rebased;
-  std::vector<uint64_t> words;
-  for (size_t off = 0; off < n; off += c->cap) {
-    uint64_t m = std::min<uint64_t>(c->cap, n - off);
-    uint64_t mb0 = offs[off], mb1 = offs[off + m];
-    if (mb1 < mb0) return CESS_BLS_E_INVALID_ARG;
-    rebased.resize(m + 1);
-    for (uint64_t j = 0; j <= m; j++) {
-      if (j && offs[off + j] < offs[off + j - 1]) return CESS_BLS_E_INVALID_ARG;
-      rebased[j] = offs[off + j] - mb0;
-    }
-    r = CESS_BLS_OK;
-    r |= c->in_sigs.ensure(m * 48);
-    r |= c->in_pks.ensure(m * 96);
-    r |= c->in_msgs.ensure(std::max<uint64_t>(mb1 - mb0, 1));
-    r |= c->in_offs.ensure((m + 1) * 8);
-    if (gt_out) r |= c->out_gt.ensure(m * 576);
-    if (r) return CESS_BLS_E_OOM;
-    HIPCHK(hipMemcpyAsync(c->in_sigs.p, sigs + 48 * off, m * 48, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->in_pks.p, pks + 96 * off, m * 96, hipMemcpyHostToDevice, s));
-    if (mb1 > mb0) HIPCHK(hipMemcpyAsync(c->in_msgs.p, msgs + mb0, mb1 - mb0, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->in_offs.p, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-    const uint8_t* dpre = nullptr;
-    if (pre) {
-      HIPCHK(hipMemcpyAsync(c->pre.p, pre + off, m, hipMemcpyHostToDevice, s));
-      dpre = c->pre.as<uint8_t>();
-    }
-    if (gt_out) HIPCHK(hipMemsetAsync(c->out_gt.p, 0, m * 576, s));
-    r = run_chunk(c, s, m, c->in_sigs.as<uint8_t>(), c->in_pks.as<uint8_t>(), c->in_msgs.as<uint8_t>(),
-                  c->in_offs.as<uint64_t>(), dpre, c->code.as<uint8_t>(), c->bitmap.as<uint64_t>(),
-                  gt_out ? c->out_gt.as<uint8_t>() : nullptr);
-    if (r) return r;
-    if (codes_out) HIPCHK(hipMemcpyAsync(codes_out + off, c->code.p, m, hipMemcpyDeviceToHost, s));
-    if (gt_out) HIPCHK(hipMemcpyAsync(gt_out + 576 * off, c->out_gt.p, m * 576, hipMemcpyDeviceToHost, s));
-    uint64_t nw = (m + 63) / 64;
-    words.resize(nw);
-    HIPCHK(hipMemcpyAsync(words.data(), c->bitmap.p, nw * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (bitmap_out) memcpy(bitmap_out + off / 64, words.data(), nw * 8);
-    r = collect_profile(c, s);
-    if (r) return r;
-  }
   return order_end(c, s);
 }
 
@@ -508,26 +378,6 @@ int cess_host::verify_var_host(cess_bls_ctx* c, size_t n, const uint8_t* sig_dat
   }
   return verify_host(c, n, sigs.data(), pks.data(), msgs, msg_offsets, pre.data(), codes_out, bitmap_out, nullptr);
 }
-
-// multi-device forms (host_multi.cpp)
-int cess_multi_verify(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
-                      const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out, bool rlc, const uint8_t* seed32,
-                      uint64_t* stats4);
-int cess_multi_verify_var(cess_bls_ctx* c, size_t n, const uint8_t* sig_data, const uint64_t* sig_offsets,
-                          const uint8_t* pk_data, const uint64_t* pk_offsets, const uint8_t* msgs,
-                          const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out);
-int cess_multi_keyed(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx, const uint8_t* msgs,
-                     const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out);
-int cess_multi_keys_load(cess_bls_ctx* c, size_t k, const uint8_t* pks, uint8_t* key_codes_out);
-int cess_multi_gen(cess_bls_ctx* c, int kind, size_t n, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs,
-                   uint8_t* out);
-int cess_multi_gt(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
-                  const uint64_t* offs, uint8_t* codes_out, uint8_t* gt_out);
-
-#define ENTRY(c)                          \
-  if (!(c)) return CESS_BLS_E_INVALID_ARG; \
-  CtxLock lock_(c);                        \
-  if (!lock_.ok()) return CESS_BLS_E_BUSY
 
 extern "C" int cess_bls_verify_batch(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks,
                                      const uint8_t* msgs, const uint64_t* msg_offsets, uint8_t* codes_out,
@@ -613,12 +463,8 @@ extern "C" int cess_bls_verify_batch_device(cess_bls_ctx* c, size_t n, const uin
     r = run_chunk(c, s, m, d_sigs + 48 * off, d_pks + 96 * off, d_msgs, d_offs + off, nullptr, d_codes + off,
                   d_bitmap ? d_bitmap + off / 64 : c->bitmap.as<uint64_t>(), nullptr);
     if (r) return r;
-    if (c->flags & CESS_BLS_F_PROFILE) {
-      r = collect_profile(c, s);
-      if (r) return r;
-    }
   }
-  return order_end(c, s);
+  return call_end(c, s);
 }
 
 // distinct-key table ---------------------------------------------------------
@@ -671,9 +517,7 @@ extern "C" int cess_bls_keys_load(cess_bls_ctx* c, size_t k, const uint8_t* pks,
 static int run_chunk_keyed(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uint8_t* sigs, const uint32_t* idx,
                            const uint8_t* msgs, const uint64_t* offs, uint8_t* codes, uint64_t* bitmap) {
   for (int k = 0; k < (n > c->qcap ? 2 : 1); k++)
-    if (c->slot[k].inf.ensure(c->qcap) | c->slot[k].sig_aff.ensure(c->qcap * CESS_W_G1 * 4) |
-        c->slot[k].h_aff.ensure(c->qcap * CESS_W_G1 * 4))
-      return CESS_BLS_E_OOM;
+    if (c->slot[k].ensure(c->qcap, false)) return CESS_BLS_E_OOM;
   auto light = [&](StageSlot& S, uint64_t q, uint64_t off, uint64_t m, hipStream_t t) -> int {
     const unsigned g = grid_for(m);
     uint8_t* inf = S.inf.as<uint8_t>();
@@ -687,7 +531,6 @@ static int run_chunk_keyed(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uin
     return CESS_BLS_OK;
   };
   auto heavy = [&](StageSlot& S, uint64_t q, uint64_t off, uint64_t m) -> int {
-    const unsigned g = grid_for(m);
     LAUNCH(ST_MILLER, s, miller_kernel(), miller_grid(m), miller_block(), 0, s, m, (const uint8_t*)(codes + off),
            (const uint8_t*)S.inf.as<uint8_t>(), (const uint32_t*)S.sig_aff.as<uint32_t>(),
            (const uint32_t*)S.h_aff.as<uint32_t>(), (const uint32_t*)c->neg_g2.as<uint32_t>(),
@@ -719,54 +562,76 @@ extern "C" int cess_bls_verify_batch_keyed_device(cess_bls_ctx* c, size_t n, con
     r = run_chunk_keyed(c, s, m, d_sigs + 48 * off, d_key_idx + off, d_msgs, d_offs + off, d_codes + off,
                         d_bitmap ? d_bitmap + off / 64 : c->bitmap.as<uint64_t>());
     if (r) return r;
-    r = collect_profile(c, s);
-    if (r) return r;
   }
-  return order_end(c, s);
+  return call_end(c, s);
 }
 
-int cess_keyed_one(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx, const uint8_t* msgs,
-                   const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out) {
-  if (n == 0) return CESS_BLS_OK;
-  if (!sigs || !key_idx || !offs || (!msgs && offs[n] != offs[0])) return CESS_BLS_E_INVALID_ARG;
-  if (c->nkeys == 0) return CESS_BLS_E_INVALID_ARG;
-  // an out-of-range key index is a caller error on the host-buffer API
-  for (size_t i = 0; i < n; i++)
-    if (key_idx[i] >= c->nkeys) return CESS_BLS_E_INVALID_ARG;
+// Host-buffer per-signature batch in chunks of cap records: each chunk's
+// records are staged, run (run_chunk over pks, or run_chunk_keyed over key_idx
+// when that is given) and its codes, bitmap words and Gt values copied back.
+// msg offsets are absolute into msgs; each chunk is rebased.  pre: optional
+// host pre-flags; gt_out: optional.
+static int host_chunks(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint32_t* key_idx,
+                       const uint8_t* msgs, const uint64_t* offs, const uint8_t* pre, uint8_t* codes_out,
+                       uint64_t* bitmap_out, uint8_t* gt_out) {
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   int r = order_begin(c, s);
   if (r) return r;
   std::vector<uint64_t> rebased, words;
   for (size_t off = 0; off < n; off += c->cap) {
-    uint64_t m = std::min<uint64_t>(c->cap, n - off);
-    uint64_t mb0 = offs[off], mb1 = offs[off + m];
-    if (mb1 < mb0) return CESS_BLS_E_INVALID_ARG;
-    rebased.resize(m + 1);
-    for (uint64_t j = 0; j <= m; j++) {
-      if (j && offs[off + j] < offs[off + j - 1]) return CESS_BLS_E_INVALID_ARG;
-      rebased[j] = offs[off + j] - mb0;
-    }
-    r = c->in_sigs.ensure(m * 48) | c->in_idx.ensure(m * 4) | c->in_msgs.ensure(std::max<uint64_t>(mb1 - mb0, 1)) |
-        c->in_offs.ensure((m + 1) * 8);
+    const uint64_t m = std::min<uint64_t>(c->cap, n - off);
+    uint64_t mb0, mb;
+    if (!rebase_offsets(offs, off, m, msgs != nullptr, rebased, &mb0, &mb)) return CESS_BLS_E_INVALID_ARG;
+    r = c->in_sigs.ensure(m * 48) | (key_idx ? c->in_idx.ensure(m * 4) : c->in_pks.ensure(m * 96));
+    if (gt_out) r |= c->out_gt.ensure(m * 576);
     if (r) return CESS_BLS_E_OOM;
+    r = upload_msgs(s, msgs, mb0, mb, rebased, c->in_msgs, c->in_offs);
+    if (r) return r;
     HIPCHK(hipMemcpyAsync(c->in_sigs.p, sigs + 48 * off, m * 48, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->in_idx.p, key_idx + off, m * 4, hipMemcpyHostToDevice, s));
-    if (mb1 > mb0) HIPCHK(hipMemcpyAsync(c->in_msgs.p, msgs + mb0, mb1 - mb0, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->in_offs.p, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-    r = run_chunk_keyed(c, s, m, c->in_sigs.as<uint8_t>(), c->in_idx.as<uint32_t>(), c->in_msgs.as<uint8_t>(),
-                        c->in_offs.as<uint64_t>(), c->code.as<uint8_t>(), c->bitmap.as<uint64_t>());
+    if (key_idx) HIPCHK(hipMemcpyAsync(c->in_idx.p, key_idx + off, m * 4, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(c->in_pks.p, pks + 96 * off, m * 96, hipMemcpyHostToDevice, s));
+    const uint8_t* dpre = nullptr;
+    if (pre) {
+      HIPCHK(hipMemcpyAsync(c->pre.p, pre + off, m, hipMemcpyHostToDevice, s));
+      dpre = c->pre.as<uint8_t>();
+    }
+    if (gt_out) HIPCHK(hipMemsetAsync(c->out_gt.p, 0, m * 576, s));
+    if (key_idx)
+      r = run_chunk_keyed(c, s, m, c->in_sigs.as<uint8_t>(), c->in_idx.as<uint32_t>(), c->in_msgs.as<uint8_t>(),
+                          c->in_offs.as<uint64_t>(), c->code.as<uint8_t>(), c->bitmap.as<uint64_t>());
+    else
+      r = run_chunk(c, s, m, c->in_sigs.as<uint8_t>(), c->in_pks.as<uint8_t>(), c->in_msgs.as<uint8_t>(),
+                    c->in_offs.as<uint64_t>(), dpre, c->code.as<uint8_t>(), c->bitmap.as<uint64_t>(),
+                    gt_out ? c->out_gt.as<uint8_t>() : nullptr);
     if (r) return r;
     if (codes_out) HIPCHK(hipMemcpyAsync(codes_out + off, c->code.p, m, hipMemcpyDeviceToHost, s));
-    uint64_t nw = (m + 63) / 64;
+    if (gt_out) HIPCHK(hipMemcpyAsync(gt_out + 576 * off, c->out_gt.p, m * 576, hipMemcpyDeviceToHost, s));
+    const uint64_t nw = (m + 63) / 64;
     words.resize(nw);
     HIPCHK(hipMemcpyAsync(words.data(), c->bitmap.p, nw * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(s));   // rebased and words are reused by the next chunk
     if (bitmap_out) memcpy(bitmap_out + off / 64, words.data(), nw * 8);
-    r = collect_profile(c, s);
-    if (r) return r;
   }
-  return order_end(c, s);
+  return call_end(c, s);
+}
+
+int cess_host::verify_host(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
+                           const uint64_t* offs, const uint8_t* pre, uint8_t* codes_out, uint64_t* bitmap_out,
+                           uint8_t* gt_out) {
+  if (n == 0) return CESS_BLS_OK;
+  if (!sigs || !pks || !offs || (!msgs && offs[n] != offs[0])) return CESS_BLS_E_INVALID_ARG;
+  return host_chunks(c, n, sigs, pks, nullptr, msgs, offs, pre, codes_out, bitmap_out, gt_out);
+}
+
+int cess_keyed_one(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx, const uint8_t* msgs,
+                   const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out) {
+  if (n == 0) return CESS_BLS_OK;
+  if (!sigs || !key_idx || !offs || (!msgs && offs[n] != offs[0]) || c->nkeys == 0) return CESS_BLS_E_INVALID_ARG;
+  // an out-of-range key index is a caller error on the host-buffer API
+  for (size_t i = 0; i < n; i++)
+    if (key_idx[i] >= c->nkeys) return CESS_BLS_E_INVALID_ARG;
+  return host_chunks(c, n, sigs, nullptr, key_idx, msgs, offs, nullptr, codes_out, bitmap_out, nullptr);
 }
 
 extern "C" int cess_bls_verify_batch_keyed(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx,
@@ -790,20 +655,16 @@ int cess_gen_one(cess_bls_ctx* c, int kind, size_t n, const uint8_t* sks, const 
   std::vector<uint64_t> rebased;
   for (size_t off = 0; off < n; off += c->cap) {
     uint64_t m = std::min<uint64_t>(c->cap, n - off);
+    uint64_t mb0 = 0, mb = 0;
+    if (kind != 0 && !rebase_offsets(offs, off, m, msgs != nullptr, rebased, &mb0, &mb)) return CESS_BLS_E_INVALID_ARG;
     r = c->out_bytes.ensure(m * ob);
     if (kind != 2) r |= c->in_sks.ensure(m * 32);
     if (r) return CESS_BLS_E_OOM;
-    if (kind != 2) HIPCHK(hipMemcpyAsync(c->in_sks.p, sks + 32 * off, m * 32, hipMemcpyHostToDevice, s));
     if (kind != 0) {
-      uint64_t mb0 = offs[off], mb1 = offs[off + m];
-      if (mb1 < mb0) return CESS_BLS_E_INVALID_ARG;
-      rebased.resize(m + 1);
-      for (uint64_t j = 0; j <= m; j++) rebased[j] = offs[off + j] - mb0;
-      r = c->in_msgs.ensure(std::max<uint64_t>(mb1 - mb0, 1)) | c->in_offs.ensure((m + 1) * 8);
-      if (r) return CESS_BLS_E_OOM;
-      if (mb1 > mb0) HIPCHK(hipMemcpyAsync(c->in_msgs.p, msgs + mb0, mb1 - mb0, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(c->in_offs.p, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
+      r = upload_msgs(s, msgs, mb0, mb, rebased, c->in_msgs, c->in_offs);
+      if (r) return r;
     }
+    if (kind != 2) HIPCHK(hipMemcpyAsync(c->in_sks.p, sks + 32 * off, m * 32, hipMemcpyHostToDevice, s));
     unsigned g = grid_for(m);
     if (kind == 0)
       hipLaunchKernelGGL(k_keygen, dim3(g), dim3(kBlock), 0, s, m, c->in_sks.as<uint8_t>(), c->out_bytes.as<uint8_t>());
@@ -851,11 +712,7 @@ extern "C" int cess_bls_sign_batch_device(cess_bls_ctx* c, size_t n, const uint8
   if (r) return r;
   LAUNCH(ST_SIGN, s, k_sign, dim3(grid_for(n)), dim3(kBlock), 0, s, (uint64_t)n, d_sks, d_msgs, d_offs, d_sigs_out);
   HIPCHK(hipGetLastError());
-  if (c->flags & CESS_BLS_F_PROFILE) {
-    r = collect_profile(c, s);
-    if (r) return r;
-  }
-  return order_end(c, s);
+  return call_end(c, s);
 }
 
 extern "C" int cess_bls_hash_to_g1_batch(cess_bls_ctx* c, size_t n, const uint8_t* msgs, const uint64_t* offs,

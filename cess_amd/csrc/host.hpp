@@ -1,10 +1,15 @@
 // Internal declarations shared by the host translation units behind
 // include/cess_bls.h (host.cpp: per-device context and the per-signature
 // pipeline; host_rlc.cpp: RLC batch mode; host_multi.cpp: RCCL communicator,
-// sharded batches and multi-device contexts).  Not part of the C ABI.
+// sharded batches and multi-device contexts; host_rsa.cpp: RSA batches;
+// host_service.cpp: deserialize batch and verdict cache): the context, the
+// entry-point and launch macros, the choice of the heavy kernels, message
+// staging and the workers one file defines for another.  The index arithmetic
+// that needs no HIP is in host_pure.hpp.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -14,6 +19,7 @@
 #include "../../include/cess_bls.h"
 #include "../../include/cess_rsa.h"
 #include "comm.hpp"
+#include "host_pure.hpp"
 #include "kernels.hpp"
 
 // kernels (k_*.hip)
@@ -138,6 +144,13 @@ struct RlcState {
 // Stage buffers of one in-flight pipeline part (SoA, stride = qcap).
 struct StageSlot {
   DevBuf inf, sig_aff, h_aff, pk_aff, coeffs;
+  // the per-record key buffers (19.6 KB of line coefficients per signature)
+  // only with_key_buffers: keyed batches never allocate them
+  int ensure(uint64_t qcap, bool with_key_buffers) {
+    int r = inf.ensure(qcap) | sig_aff.ensure(qcap * CESS_W_G1 * 4) | h_aff.ensure(qcap * CESS_W_G1 * 4);
+    if (with_key_buffers) r |= pk_aff.ensure(qcap * CESS_W_G2 * 4) | coeffs.ensure(qcap * (uint64_t)CESS_W_COEFFS * 4);
+    return r ? CESS_BLS_E_OOM : CESS_BLS_OK;
+  }
 };
 
 // One profiled kernel launch: [a, b] events on the launch's stream.
@@ -149,7 +162,6 @@ struct ProfRec {
 }  // namespace cess_host
 
 struct RsaState;   // host_rsa.cpp
-void cess_rsa_state_free(cess_bls_ctx* c);
 
 struct cess_bls_ctx {
   int device = 0;
@@ -212,6 +224,25 @@ struct cess_bls_ctx {
     if ((x) != hipSuccess) return CESS_BLS_E_HIP; \
   } while (0)
 
+// every locking entry point: a context, held by this thread alone
+#define ENTRY(c)                           \
+  if (!(c)) return CESS_BLS_E_INVALID_ARG; \
+  CtxLock lock_(c);                        \
+  if (!lock_.ok()) return CESS_BLS_E_BUSY
+
+// One kernel launch of context `c` on stream strm, bracketed by a pair of
+// HIP events under CESS_BLS_F_PROFILE (bench.py's rooflines take the kernels'
+// durations from them); call_end collects the records.
+#define LAUNCH(stage, strm, ...)                \
+  do {                                          \
+    hipEvent_t pa_;                             \
+    int pr_ = prof_begin(c, strm, stage, &pa_); \
+    if (pr_) return pr_;                        \
+    hipLaunchKernelGGL(__VA_ARGS__);            \
+    pr_ = prof_end(c, strm, stage, pa_);        \
+    if (pr_) return pr_;                        \
+  } while (0)
+
 namespace cess_host {
 
 // RAII guard for the one-thread-at-a-time contract
@@ -237,7 +268,20 @@ int verify_host(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* p
 int verify_var_host(cess_bls_ctx* c, size_t n, const uint8_t* sig_data, const uint64_t* sig_offsets,
                     const uint8_t* pk_data, const uint64_t* pk_offsets, const uint8_t* msgs, const uint64_t* msg_offsets,
                     uint8_t* codes_out, uint64_t* bitmap_out);
-int collect_profile(cess_bls_ctx* c, hipStream_t s);
+// End of an entry point's work on s: the call's profile records go into the
+// stage totals and their events back to the pool, then order_end.  Without
+// CESS_BLS_F_PROFILE this is order_end alone; with it, it waits for the
+// context's streams, so callers that hand results back call it after the
+// synchronisation they need anyway.
+int call_end(cess_bls_ctx* c, hipStream_t s);
+
+// Upload one staged message range (rebase_offsets, host_pure.hpp): bytes
+// [first, first + bytes) of msgs into d_msgs, which is allocated `slack` bytes
+// longer (at least one byte in all), and the rebased offsets into d_offs, on
+// s.  `rebased` is the source of an asynchronous copy: the caller neither
+// reuses nor frees it before it has synchronised s.
+int upload_msgs(hipStream_t s, const uint8_t* msgs, uint64_t first, uint64_t bytes,
+                const std::vector<uint64_t>& rebased, DevBuf& d_msgs, DevBuf& d_offs, uint64_t slack = 0);
 // RLC (host_rlc.cpp)
 int rlc_begin(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
               const uint64_t* offs, const uint8_t* seed32, uint8_t* gt_out);
@@ -252,7 +296,88 @@ int verify_rlc_host(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_
                     uint64_t* stats4);
 // OS randomness for RLC seeds drawn by the library (mode = RLC)
 int os_random(uint8_t* out, size_t n);
-// bitmap words from codes (host)
-void bitmap_from_codes(const uint8_t* codes, uint64_t n, uint64_t* words);
+
+// The heavy kernels.  Miller loop: k_miller2 (default: a lane pair per
+// signature, 256-thread blocks of 128 signatures, two waves per SIMD;
+// bls/pair.hpp) or k_miller (one lane per signature, one wave per SIMD), env
+// CESS_BLS_MILLER = lane, read once per process.  Both take the same arguments
+// and write the same fval rows; k_miller2 runs config[1]'s Miller loop in
+// 129.8-130.0 ms per 1 M against 149.5-149.7 (same box,
+// profiles/round6_c_sweep_miller_pair.txt).  The distinct-key RLC's
+// k_miller_rr2 / k_miller_rr follow the same choice.
+typedef void (*MillerKernel)(uint64_t, const uint8_t*, const uint8_t*, const uint32_t*, const uint32_t*,
+                             const uint32_t*, const uint4*, uint4*, uint4*, uint64_t, const uint32_t*, uint64_t,
+                             const uint8_t*);
+typedef void (*MillerRrKernel)(uint64_t, uint64_t, const uint8_t*, const uint8_t*, const uint32_t*, const uint4*,
+                               uint4*, uint64_t, uint64_t);
+inline bool miller_pair() {
+  static const bool v = [] {
+    const char* e = getenv("CESS_BLS_MILLER");
+    return !(e && strcmp(e, "lane") == 0);
+  }();
+  return v;
+}
+inline MillerKernel miller_kernel() { return miller_pair() ? k_miller2 : k_miller; }
+inline MillerRrKernel miller_rr_kernel() { return miller_pair() ? k_miller_rr2 : k_miller_rr; }
+// the lane-pair kernels: blocks of CESS_PAIR_THREADS / 2 signatures
+constexpr uint64_t kPairSigs = CESS_PAIR_THREADS / 2;
+// (covering whole 64-record bitmap words: k_final2 writes 32-bit halves, one per
+// wave of 32 signatures, so both waves of a word must exist)
+inline unsigned pair_grid(uint64_t m) {
+  const uint64_t m64 = (m + 63) & ~63ull;
+  return (unsigned)((m64 + kPairSigs - 1) / kPairSigs);
+}
+inline dim3 miller_grid(uint64_t m) { return dim3(miller_pair() ? pair_grid(m) : grid_for(m)); }
+inline dim3 miller_block() { return dim3(miller_pair() ? CESS_PAIR_THREADS : kBlock); }
+
+// The final-exponentiation kernel: k_final2 (default: a lane pair per
+// signature, the accumulator in LDS; bls/pair_fe.hpp) or k_final (one lane per
+// signature, accumulators in HBM), env CESS_BLS_FINAL = lane.  Same arguments
+// and outputs; k_final2 137.4-138.2 against 142.1 ms per 1 M on one box, ~99
+// against ~332 KB/sig counted traffic (profiles/round6_e_sweep_final_pair.txt).
+typedef void (*FinalKernel)(uint64_t, uint8_t*, uint4*, uint4*, uint64_t*, uint8_t*, uint64_t);
+inline bool final_pair() {
+  static const bool v = [] {
+    const char* e = getenv("CESS_BLS_FINAL");
+    return !(e && strcmp(e, "lane") == 0);
+  }();
+  return v;
+}
+inline FinalKernel final_kernel() { return final_pair() ? k_final2 : k_final; }
+inline dim3 final_grid(uint64_t m) { return dim3(final_pair() ? pair_grid(m) : grid_for(m)); }
+inline dim3 final_block() { return dim3(final_pair() ? CESS_PAIR_THREADS : kBlock); }
 
 }  // namespace cess_host
+
+// Workers that one host file defines and another calls (not part of the C ABI).
+// single-device forms of the multi-device entry points (host.cpp, host_rsa.cpp)
+int cess_keys_load_one(cess_bls_ctx* c, size_t k, const uint8_t* pks, uint8_t* key_codes_out);
+int cess_keyed_one(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx, const uint8_t* msgs,
+                   const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_gen_one(cess_bls_ctx* c, int kind, size_t n, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs,
+                 uint8_t* out);
+int cess_rsa_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
+                 const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_rsa_sha256_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
+                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
+void cess_rsa_state_free(cess_bls_ctx* c);
+// one process, several GPUs (host_multi.cpp)
+int cess_multi_create(const cess_bls_config* cfg, int ndev, cess_bls_ctx* c);
+int cess_multi_verify(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
+                      const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out, bool rlc, const uint8_t* seed32,
+                      uint64_t* stats4);
+int cess_multi_verify_var(cess_bls_ctx* c, size_t n, const uint8_t* sig_data, const uint64_t* sig_offsets,
+                          const uint8_t* pk_data, const uint64_t* pk_offsets, const uint8_t* msgs,
+                          const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_multi_keyed(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx, const uint8_t* msgs,
+                     const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_multi_keys_load(cess_bls_ctx* c, size_t k, const uint8_t* pks, uint8_t* key_codes_out);
+int cess_multi_gen(cess_bls_ctx* c, int kind, size_t n, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs,
+                   uint8_t* out);
+int cess_multi_gt(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
+                  const uint64_t* offs, uint8_t* codes_out, uint8_t* gt_out);
+int cess_multi_rsa(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
+                   const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_multi_rsa_sha256(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                          const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                          uint64_t* bitmap_out);

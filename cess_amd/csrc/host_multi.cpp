@@ -33,18 +33,6 @@ using namespace cess_host;
     if ((x) != ncclSuccess) return CESS_BLS_E_RCCL; \
   } while (0)
 
-#define ENTRY(c)                          \
-  if (!(c)) return CESS_BLS_E_INVALID_ARG; \
-  CtxLock lock_(c);                        \
-  if (!lock_.ok()) return CESS_BLS_E_BUSY
-
-// single-device workers (host.cpp)
-int cess_keys_load_one(cess_bls_ctx* c, size_t k, const uint8_t* pks, uint8_t* key_codes_out);
-int cess_keyed_one(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint32_t* key_idx, const uint8_t* msgs,
-                   const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out);
-int cess_gen_one(cess_bls_ctx* c, int kind, size_t n, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs,
-                 uint8_t* out);
-
 // ---------------------------------------------------------------------------
 // RCCL transport (comm.hpp): production, one process per GPU, xGMI
 // ---------------------------------------------------------------------------
@@ -428,7 +416,6 @@ extern "C" int cess_bls_verify_batch_sharded_device(cess_bls_ctx* c, size_t n_to
     const uint64_t q = std::min<uint64_t>(c->cap, m - off);
     r = run_chunk(c, s, q, d_sigs + 48 * off, d_pks + 96 * off, d_msgs, d_offs + off, nullptr, codes + off,
                   my_words + off / 64, nullptr);
-    if (!r && (c->flags & CESS_BLS_F_PROFILE)) r = collect_profile(c, s);
   }
   if (r) {
     // past the agreement the peers are committed to the all-gathers: take part
@@ -444,7 +431,7 @@ extern "C" int cess_bls_verify_batch_sharded_device(cess_bls_ctx* c, size_t n_to
     const int g2 = t.allgather_dev(c->device, d_codes_all, wpr * 64, s);
     if (!g) g = g2;
   }
-  const int oe = order_end(c, s);
+  const int oe = call_end(c, s);
   // (5) a second status agreement, ordered after the all-gathers (the
   // transport's host collectives wait for the context's last stream): a
   // failure on any rank after (3) is returned on every rank
@@ -638,9 +625,6 @@ int cess_multi_gt(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t*
   });
 }
 
-int cess_rsa_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
-                 const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
-
 int cess_multi_rsa(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                    const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out) {
   if (n == 0) return CESS_BLS_OK;
@@ -653,9 +637,6 @@ int cess_multi_rsa(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uin
 
 // hashed mode (RSASSA-PKCS1-v1_5 with SHA-256): the same sharding; each device
 // hashes and verifies its own records
-int cess_rsa_sha256_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
-                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
-
 int cess_multi_rsa_sha256(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
                           const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
                           uint64_t* bitmap_out) {

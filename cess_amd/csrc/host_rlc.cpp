@@ -13,20 +13,7 @@
 using namespace cess_host;
 
 namespace {
-constexpr uint64_t kRlcLeaf = 2048;
-
-// per-kernel HIP-event records of the RLC path's chunk kernels (with
-// CESS_BLS_F_PROFILE; host.cpp LAUNCH): bench.py's RLC lines take their
-// roofline from these (the Miller stage is k_miller_rr in the distinct-key mode)
-#define RLAUNCH(stage, strm, ...)                        \
-  do {                                                   \
-    hipEvent_t pa_;                                      \
-    int pr_ = prof_begin(c, strm, stage, &pa_);          \
-    if (pr_) return pr_;                                 \
-    hipLaunchKernelGGL(__VA_ARGS__);                     \
-    pr_ = prof_end(c, strm, stage, pa_);                 \
-    if (pr_) return pr_;                                 \
-  } while (0)   // records verified per signature
+constexpr uint64_t kRlcLeaf = 2048;   // records verified per signature
 constexpr uint64_t kRlcFan = 16;      // bisection fan-out per level
 // distinct-key mode: a level re-multiplies stored Miller values and costs one
 // single-wave Miller loop and final exponentiation of latency whatever its
@@ -527,8 +514,7 @@ static int rlcd_begin(cess_bls_ctx* c, RlcState& R, const uint8_t* seed32, uint6
   r |= R.d_rec_f.ensure(((n + kRlcdPer - 1) / kRlcdPer) * CESS_W_FP12 * 4) | R.d_seed.ensure(32) | R.rec_h.ensure(q * CESS_W_G1 * 4);
   r |= R.rec_inf.ensure(q);
   StageSlot& S = c->slot[0];
-  r |= S.inf.ensure(q) | S.sig_aff.ensure(q * CESS_W_G1 * 4) | S.h_aff.ensure(q * CESS_W_G1 * 4) |
-       S.pk_aff.ensure(q * CESS_W_G2 * 4) | S.coeffs.ensure(q * (uint64_t)CESS_W_COEFFS * 4);
+  r |= S.ensure(q, true);
   if (r) return CESS_BLS_E_OOM;
   {
     uint32_t sw[8];
@@ -545,20 +531,13 @@ static int rlcd_begin(cess_bls_ctx* c, RlcState& R, const uint8_t* seed32, uint6
   const uint64_t step = q >= kRlcdPer ? q - q % kRlcdPer : q;
   for (uint64_t off = 0; off < n; off += step) {
     const uint64_t m = std::min<uint64_t>(step, n - off);
-    const uint64_t mb0 = R.offs[off], mb1 = R.offs[off + m];
-    if (mb1 < mb0) return CESS_BLS_E_INVALID_ARG;
-    rebased.resize(m + 1);
-    for (uint64_t j = 0; j <= m; j++) {
-      if (j && R.offs[off + j] < R.offs[off + j - 1]) return CESS_BLS_E_INVALID_ARG;
-      rebased[j] = R.offs[off + j] - mb0;
-    }
-    r = c->in_sigs.ensure(m * 48) | c->in_pks.ensure(m * 96) | c->in_msgs.ensure(std::max<uint64_t>(mb1 - mb0, 1)) |
-        c->in_offs.ensure((m + 1) * 8);
-    if (r) return CESS_BLS_E_OOM;
+    uint64_t mb0, mb;
+    if (!rebase_offsets(R.offs, off, m, R.msgs != nullptr, rebased, &mb0, &mb)) return CESS_BLS_E_INVALID_ARG;
+    if (c->in_sigs.ensure(m * 48) | c->in_pks.ensure(m * 96)) return CESS_BLS_E_OOM;
+    r = upload_msgs(s, R.msgs, mb0, mb, rebased, c->in_msgs, c->in_offs);
+    if (r) return r;
     HIPCHK(hipMemcpyAsync(c->in_sigs.p, R.sigs + 48 * off, m * 48, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->in_pks.p, R.pks + 96 * off, m * 96, hipMemcpyHostToDevice, s));
-    if (mb1 > mb0) HIPCHK(hipMemcpyAsync(c->in_msgs.p, R.msgs + mb0, mb1 - mb0, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->in_offs.p, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
     uint8_t* code = R.d_code.as<uint8_t>() + off;
     uint8_t* inf = S.inf.as<uint8_t>();
     HIPCHK(hipMemsetAsync(code, 0, m, s));
@@ -566,14 +545,14 @@ static int rlcd_begin(cess_bls_ctx* c, RlcState& R, const uint8_t* seed32, uint6
     const unsigned g = grid_for(m);
     // the per-signature decode / hash / prepare (run_chunk's light kernels;
     // codes in the reference's precedence)
-    RLAUNCH(ST_DECODE_SIG, s, k_decode_sig, dim3(g), dim3(kBlock), 0, s, m, c->in_sigs.as<uint8_t>(), (const uint8_t*)nullptr,
-                       code, inf, S.sig_aff.as<uint32_t>(), q);
-    RLAUNCH(ST_DECODE_PK, s, k_decode_pk, dim3(g), dim3(kBlock), 0, s, m, c->in_pks.as<uint8_t>(), (const uint8_t*)nullptr,
-                       code, inf, S.pk_aff.as<uint32_t>(), q, strict);
-    RLAUNCH(ST_HASH, s, k_hash, dim3(g), dim3(kBlock), 0, s, m, c->in_msgs.as<uint8_t>(), c->in_offs.as<uint64_t>(),
-                       (const uint8_t*)code, S.h_aff.as<uint32_t>(), q);
-    RLAUNCH(ST_PREPARE, s, k_prepare, dim3(g), dim3(kBlock), 0, s, m, (const uint32_t*)S.pk_aff.as<uint32_t>(),
-                       S.coeffs.as<uint4>(), q, code, (const uint8_t*)inf);
+    LAUNCH(ST_DECODE_SIG, s, k_decode_sig, dim3(g), dim3(kBlock), 0, s, m, c->in_sigs.as<uint8_t>(), (const uint8_t*)nullptr,
+           code, inf, S.sig_aff.as<uint32_t>(), q);
+    LAUNCH(ST_DECODE_PK, s, k_decode_pk, dim3(g), dim3(kBlock), 0, s, m, c->in_pks.as<uint8_t>(), (const uint8_t*)nullptr,
+           code, inf, S.pk_aff.as<uint32_t>(), q, strict);
+    LAUNCH(ST_HASH, s, k_hash, dim3(g), dim3(kBlock), 0, s, m, c->in_msgs.as<uint8_t>(), c->in_offs.as<uint64_t>(),
+           (const uint8_t*)code, S.h_aff.as<uint32_t>(), q);
+    LAUNCH(ST_PREPARE, s, k_prepare, dim3(g), dim3(kBlock), 0, s, m, (const uint32_t*)S.pk_aff.as<uint32_t>(),
+           S.coeffs.as<uint4>(), q, code, (const uint8_t*)inf);
     // P_i = r_i sig_i, Q_i = r_i H_i (stride n), then f_i = Miller(Q_i, pk_i)
     hipLaunchKernelGGL(k_rlcd_scale, dim3(g), dim3(kBlock), 0, s, m, (const uint8_t*)code, (const uint8_t*)inf,
                        (const uint32_t*)S.sig_aff.as<uint32_t>(), (const uint32_t*)S.h_aff.as<uint32_t>(),
@@ -588,14 +567,11 @@ static int rlcd_begin(cess_bls_ctx* c, RlcState& R, const uint8_t* seed32, uint6
     // g_k straight into the batch-wide lane values (stride ceil(n / P))
     const uint64_t np = (m + kRlcdPer - 1) / kRlcdPer;
     // (k_miller_rr2: a lane pair per lane of records, two waves per SIMD,
-    // unless CESS_BLS_MILLER=lane selects the one-lane kernels)
-    static const bool rr_pair = !(getenv("CESS_BLS_MILLER") && strcmp(getenv("CESS_BLS_MILLER"), "lane") == 0);
-    RLAUNCH(ST_MILLER, s, rr_pair ? k_miller_rr2 : k_miller_rr,
-            dim3(rr_pair ? (unsigned)((np + CESS_PAIR_THREADS / 2 - 1) / (CESS_PAIR_THREADS / 2)) : grid_for(np)),
-            dim3(rr_pair ? CESS_PAIR_THREADS : kBlock), 0, s, np, m, (const uint8_t*)code,
-                       (const uint8_t*)R.rec_inf.as<uint8_t>(), (const uint32_t*)R.rec_h.as<uint32_t>(),
-                       (const uint4*)S.coeffs.as<uint4>(), R.d_rec_f.as<uint4>() + off / kRlcdPer, q,
-                       (n + kRlcdPer - 1) / kRlcdPer);
+    // unless the one-lane kernels are selected: miller_pair(), host.hpp)
+    LAUNCH(ST_MILLER, s, miller_rr_kernel(), miller_grid(np), miller_block(), 0, s, np, m, (const uint8_t*)code,
+           (const uint8_t*)R.rec_inf.as<uint8_t>(), (const uint32_t*)R.rec_h.as<uint32_t>(),
+           (const uint4*)S.coeffs.as<uint4>(), R.d_rec_f.as<uint4>() + off / kRlcdPer, q,
+           (n + kRlcdPer - 1) / kRlcdPer);
     HIPCHK(hipGetLastError());
     if (last) {
       // the batch's S sum and its single-wave Miller loop on stream2, after
@@ -658,7 +634,7 @@ int cess_host::rlc_begin_at(cess_bls_ctx* c, size_t n, const uint8_t* sigs, cons
   if (c->flags & CESS_BLS_F_RLC_DISTINCT) {
     r = rlcd_begin(c, R, seed32, index_hi, gt_out);
     if (r) return r;
-    r = order_end(c, s);
+    r = call_end(c, s);
     if (r) return r;
     R.valid = true;
     return CESS_BLS_OK;
@@ -743,26 +719,20 @@ int cess_host::rlc_begin_at(cess_bls_ctx* c, size_t n, const uint8_t* sigs, cons
   std::vector<uint64_t> rebased;
   for (uint64_t off = 0; off < n; off += c->qcap) {
     const uint64_t m = std::min<uint64_t>(c->qcap, n - off);
-    const uint64_t mb0 = offs[off], mb1 = offs[off + m];
-    if (mb1 < mb0) return CESS_BLS_E_INVALID_ARG;
-    rebased.resize(m + 1);
-    for (uint64_t j = 0; j <= m; j++) {
-      if (j && offs[off + j] < offs[off + j - 1]) return CESS_BLS_E_INVALID_ARG;
-      rebased[j] = offs[off + j] - mb0;
-    }
-    r = c->in_sigs.ensure(m * 48) | c->in_msgs.ensure(std::max<uint64_t>(mb1 - mb0, 1)) | c->in_offs.ensure((m + 1) * 8);
-    if (r) return CESS_BLS_E_OOM;
+    uint64_t mb0, mb;
+    if (!rebase_offsets(offs, off, m, msgs != nullptr, rebased, &mb0, &mb)) return CESS_BLS_E_INVALID_ARG;
+    if (c->in_sigs.ensure(m * 48)) return CESS_BLS_E_OOM;
+    r = upload_msgs(s, msgs, mb0, mb, rebased, c->in_msgs, c->in_offs);
+    if (r) return r;
     HIPCHK(hipMemcpyAsync(c->in_sigs.p, sigs + 48 * off, m * 48, hipMemcpyHostToDevice, s));
-    if (mb1 > mb0) HIPCHK(hipMemcpyAsync(c->in_msgs.p, msgs + mb0, mb1 - mb0, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->in_offs.p, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
     const unsigned g = grid_for(m);
     StageSlot& S = c->slot[0];
     // the points go to the batch-wide arrays (stride n) on the bucket path
     uint32_t* sig_dst = R.pts ? R.Xs.as<uint32_t>() + off : S.sig_aff.as<uint32_t>();
     uint32_t* h_dst = R.pts ? R.Xh.as<uint32_t>() + off : S.h_aff.as<uint32_t>();
     const uint64_t pstride = R.pts ? n : c->qcap;
-    RLAUNCH(ST_DECODE_SIG, s, k_decode_sig, dim3(g), dim3(kBlock), 0, s, m, c->in_sigs.as<uint8_t>(), (const uint8_t*)nullptr,
-                       c->code.as<uint8_t>(), S.inf.as<uint8_t>(), sig_dst, pstride);
+    LAUNCH(ST_DECODE_SIG, s, k_decode_sig, dim3(g), dim3(kBlock), 0, s, m, c->in_sigs.as<uint8_t>(), (const uint8_t*)nullptr,
+           c->code.as<uint8_t>(), S.inf.as<uint8_t>(), sig_dst, pstride);
     HIPCHK(hipGetLastError());
     hc.resize(m);
     hi.resize(m);
@@ -778,8 +748,8 @@ int cess_host::rlc_begin_at(cess_bls_ctx* c, size_t n, const uint8_t* sigs, cons
     memcpy(&R.codes[off], hc.data(), m);
     HIPCHK(hipMemcpyAsync(c->code.p, hc.data(), m, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(S.inf.p, hi.data(), m, hipMemcpyHostToDevice, s));
-    RLAUNCH(ST_HASH, s, k_hash, dim3(g), dim3(kBlock), 0, s, m, c->in_msgs.as<uint8_t>(), c->in_offs.as<uint64_t>(),
-                       (const uint8_t*)c->code.as<uint8_t>(), h_dst, pstride);
+    LAUNCH(ST_HASH, s, k_hash, dim3(g), dim3(kBlock), 0, s, m, c->in_msgs.as<uint8_t>(), c->in_offs.as<uint64_t>(),
+           (const uint8_t*)c->code.as<uint8_t>(), h_dst, pstride);
     if (R.pts) {
       HIPCHK(hipMemcpyAsync(R.d_code.as<uint8_t>() + off, hc.data(), m, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(R.d_inf.as<uint8_t>() + off, hi.data(), m, hipMemcpyHostToDevice, s));
@@ -797,7 +767,7 @@ int cess_host::rlc_begin_at(cess_bls_ctx* c, size_t n, const uint8_t* sigs, cons
   r = rlc_check_multi(c, R, {{0, n}}, ok, gt_out);
   if (r) return r;
   R.local_ok = ok[0] != 0;
-  r = order_end(c, s);
+  r = call_end(c, s);
   if (r) return r;
   R.valid = true;
   return CESS_BLS_OK;
@@ -916,19 +886,8 @@ int cess_host::verify_rlc_host(cess_bls_ctx* c, size_t n, const uint8_t* sigs, c
                                uint64_t* stats4) {
   int r = rlc_begin_at(c, n, sigs, pks, msgs, offs, seed32, 0, nullptr);
   if (r) return r;
-  r = rlc_finish(c, codes_out, bitmap_out, stats4);
-  if (r) return r;
-  return collect_profile(c, c->stream);   // no-op without CESS_BLS_F_PROFILE
+  return rlc_finish(c, codes_out, bitmap_out, stats4);
 }
-
-#define ENTRY(c)                          \
-  if (!(c)) return CESS_BLS_E_INVALID_ARG; \
-  CtxLock lock_(c);                        \
-  if (!lock_.ok()) return CESS_BLS_E_BUSY
-
-int cess_multi_verify(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
-                      const uint64_t* offs, uint8_t* codes_out, uint64_t* bitmap_out, bool rlc, const uint8_t* seed32,
-                      uint64_t* stats4);
 
 extern "C" int cess_bls_rlc_begin(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks,
                                   const uint8_t* msgs, const uint64_t* offs, const uint8_t* seed32, uint8_t* gt_out) {

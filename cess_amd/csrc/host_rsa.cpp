@@ -389,39 +389,30 @@ static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_
   hipStream_t s = c->stream;
   int r = order_begin(c, s);
   if (r) return r;
-  const uint64_t sb = soffs[n] - soffs[0], mb = moffs[n] - moffs[0];
-  std::vector<uint64_t> so(n + 1), mo(n + 1);
-  for (size_t i = 0; i <= n; i++) {
-    if (i && (soffs[i] < soffs[i - 1] || moffs[i] < moffs[i - 1])) return CESS_BLS_E_INVALID_ARG;
-    so[i] = soffs[i] - soffs[0];
-    mo[i] = moffs[i] - moffs[0];
-  }
-  if (S.in_idx.ensure(n * 4) | S.in_sigs.ensure(std::max<uint64_t>(sb, 1)) | S.in_soffs.ensure((n + 1) * 8) |
-      S.in_msgs.ensure(mb + 4) /* k_rsa_digest fetches whole dwords (rsa_digest.hpp) */ | S.in_moffs.ensure((n + 1) * 8) | S.out_codes.ensure(n))
-    return CESS_BLS_E_OOM;
+  // signatures and messages are both offset-indexed byte ranges; so / mo live
+  // until the synchronisation below
+  std::vector<uint64_t> so, mo;
+  uint64_t s0, sb, m0, mb;
+  if (!rebase_offsets(soffs, 0, n, sigs != nullptr, so, &s0, &sb) ||
+      !rebase_offsets(moffs, 0, n, msgs != nullptr, mo, &m0, &mb))
+    return CESS_BLS_E_INVALID_ARG;
+  if (S.in_idx.ensure(n * 4) | S.out_codes.ensure(n)) return CESS_BLS_E_OOM;
+  r = upload_msgs(s, sigs, s0, sb, so, S.in_sigs, S.in_soffs);
+  // k_rsa_digest fetches whole dwords (rsa_digest.hpp): 4 bytes of slack
+  if (!r) r = upload_msgs(s, msgs, m0, mb, mo, S.in_msgs, S.in_moffs, 4);
+  if (r) return r;
   HIPCHK(hipMemcpyAsync(S.in_idx.p, key_idx, n * 4, hipMemcpyHostToDevice, s));
-  if (sb) HIPCHK(hipMemcpyAsync(S.in_sigs.p, sigs + soffs[0], sb, hipMemcpyHostToDevice, s));
-  if (mb) HIPCHK(hipMemcpyAsync(S.in_msgs.p, msgs + moffs[0], mb, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(S.in_soffs.p, so.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(S.in_moffs.p, mo.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   r = (sha256 ? rsa_run_sha256 : rsa_run)(c, T, s, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(),
                                           S.in_soffs.as<uint64_t>(), S.in_msgs.as<uint8_t>(),
                                           S.in_moffs.as<uint64_t>(), S.out_codes.as<uint8_t>());
-  if (r) return r;
-  r = collect_profile(c, s);
   if (r) return r;
   std::vector<uint8_t> codes(n);
   HIPCHK(hipMemcpyAsync(codes.data(), S.out_codes.p, n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (codes_out) memcpy(codes_out, codes.data(), n);
   if (bitmap_out) bitmap_from_codes(codes.data(), n, bitmap_out);
-  return order_end(c, s);
+  return call_end(c, s);
 }
-
-#define ENTRY(c)                          \
-  if (!(c)) return CESS_BLS_E_INVALID_ARG; \
-  CtxLock lock_(c);                        \
-  if (!lock_.ok()) return CESS_BLS_E_BUSY
 
 extern "C" int cess_rsa_parse_key(const uint8_t* der, size_t len, int format, uint8_t* n_out, size_t n_cap,
                                   size_t* n_len, uint64_t* e_out) {
@@ -483,9 +474,6 @@ extern "C" int cess_rsa_keys_load(cess_bls_ctx* c, size_t k, const uint8_t* ders
   return cess_rsa_keys_load_policy(c, k, ders, der_offsets, format, CESS_RSA_POLICY_RSA_CRATE, key_status_out);
 }
 
-int cess_multi_rsa(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
-                   const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
-
 int cess_rsa_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                  const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out) {
   return rsa_host(s, rsa_state(s).user, n, key_idx, sigs, soffs, msgs, moffs, codes_out, bitmap_out);
@@ -512,16 +500,10 @@ extern "C" int cess_rsa_verify_batch_device(cess_bls_ctx* c, size_t n, const uin
   if (r) return r;
   r = rsa_run(c, rsa_state(c).user, s, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs, d_msg_offsets, d_codes);
   if (r) return r;
-  r = collect_profile(c, s);   // no-op without CESS_BLS_F_PROFILE
-  if (r) return r;
-  return order_end(c, s);
+  return call_end(c, s);
 }
 
 // --- hashed mode: RSASSA-PKCS1-v1_5 with SHA-256 -----------------------------
-int cess_multi_rsa_sha256(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
-                          const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
-                          uint64_t* bitmap_out);
-
 int cess_rsa_sha256_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                         const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out) {
   return rsa_host(s, rsa_state(s).user, n, key_idx, sigs, soffs, msgs, moffs, codes_out, bitmap_out, true);
@@ -550,9 +532,7 @@ extern "C" int cess_rsa_verify_sha256_batch_device(cess_bls_ctx* c, size_t n, co
   if (r) return r;
   r = rsa_run_sha256(c, rsa_state(c).user, s, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs, d_msg_offsets, d_codes);
   if (r) return r;
-  r = collect_profile(c, s);   // no-op without CESS_BLS_F_PROFILE
-  if (r) return r;
-  return order_end(c, s);
+  return call_end(c, s);
 }
 
 extern "C" int cess_rsa_verify_sha256(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, int format,
@@ -590,24 +570,17 @@ extern "C" int cess_sha256_batch(cess_bls_ctx* c, size_t n, const uint8_t* msgs,
   hipStream_t s = d->stream;
   int r = order_begin(d, s);
   if (r) return r;
-  const uint64_t mb = msg_offsets[n] - msg_offsets[0];
-  std::vector<uint64_t> mo(n + 1);
-  for (size_t i = 0; i <= n; i++) {
-    if (i && msg_offsets[i] < msg_offsets[i - 1]) return CESS_BLS_E_INVALID_ARG;
-    mo[i] = msg_offsets[i] - msg_offsets[0];
-  }
-  if (mb && !msgs) return CESS_BLS_E_INVALID_ARG;
-  if (S.in_msgs.ensure(mb + 4) | S.in_moffs.ensure((n + 1) * 8) | S.t.ensure(digest_records(n) * 32))
-    return CESS_BLS_E_OOM;
-  if (mb) HIPCHK(hipMemcpyAsync(S.in_msgs.p, msgs + msg_offsets[0], mb, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(S.in_moffs.p, mo.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  r = digest_run(d, s, n, S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.t.as<uint8_t>(), false, nullptr);
+  std::vector<uint64_t> mo;
+  uint64_t m0, mb;
+  if (!rebase_offsets(msg_offsets, 0, n, msgs != nullptr, mo, &m0, &mb)) return CESS_BLS_E_INVALID_ARG;
+  if (S.t.ensure(digest_records(n) * 32)) return CESS_BLS_E_OOM;
+  r = upload_msgs(s, msgs, m0, mb, mo, S.in_msgs, S.in_moffs, 4);
   if (r) return r;
-  r = collect_profile(d, s);
+  r = digest_run(d, s, n, S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.t.as<uint8_t>(), false, nullptr);
   if (r) return r;
   HIPCHK(hipMemcpyAsync(out32, S.t.p, n * 32, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  return order_end(d, s);
+  return call_end(d, s);
 }
 
 extern "C" int cess_rsa_verify(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, const uint8_t* msg,

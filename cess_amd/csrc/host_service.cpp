@@ -21,11 +21,6 @@
 
 using namespace cess_host;
 
-#define ENTRY(c)                          \
-  if (!(c)) return CESS_BLS_E_INVALID_ARG; \
-  CtxLock lock_(c);                        \
-  if (!lock_.ok()) return CESS_BLS_E_BUSY
-
 // ---------------------------------------------------------------------------
 // deserialize batch
 // ---------------------------------------------------------------------------

@@ -123,6 +123,36 @@ def test_rlc_cross_shard_combine(ctx):
     assert c1[1500] == 5 and c1.count(0) == 2999 and res[1][2]["leaves"] >= 1
 
 
+def test_rlc_begin_finish_collects_profile():
+    """With CESS_BLS_F_PROFILE the begin / finish entry points hand their
+    per-launch records to the stage totals on every call: each of three calls
+    on a 128-record, two-key batch reports the same decode and hash launch
+    counts, and the totals grow by exactly that much per call."""
+    from cess_amd import bls
+    c = bls.Context(max_batch=1 << 12, profile=True)
+    try:
+        packed = _pack(*_few_key_batch(c, 128, 2, 6))
+        c.stage_stats(reset=True)
+        per_call, running = [], []
+        for call in range(3):
+            gt = c.rlc_begin(*packed, seed=bytes([call + 1]) * 32)
+            codes, words, st = c.rlc_finish(c.gt_product_is_one(gt))
+            assert set(codes) == {0} and st["distinct_keys"] == 2
+            stats = c.stage_stats(reset=False)
+            running.append((stats["k_decode_sig"][1], stats["k_hash"][1]))
+        first = running[0]
+        assert first[0] >= 1 and first[1] >= 1
+        assert running == [(first[0] * k, first[1] * k) for k in (1, 2, 3)]
+        for call in range(3):
+            c.rlc_finish(c.gt_product_is_one(c.rlc_begin(*packed, seed=bytes([call + 9]) * 32)))
+            stats = c.stage_stats(reset=True)
+            per_call.append((stats["k_decode_sig"][1], stats["k_hash"][1]))
+        # the first reset also returns the three calls counted above
+        assert per_call == [(4 * first[0], 4 * first[1]), first, first]
+    finally:
+        c.close()
+
+
 def test_rlc_empty_and_tiny(ctx):
     codes, words, st = ctx.verify_rlc(b"", b"", b"", [0], seed=bytes(32))
     assert codes == b"" and st["checks"] == 0
