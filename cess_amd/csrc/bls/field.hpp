@@ -137,28 +137,14 @@ CESS_HD fp fp_reduce_once(const fp& t) {
   return r;
 }
 
-// r = t - 2p if t >= 2p  (t < 4p): back into [0, 2p)
-CESS_HD fp fp_reduce2(const fp& t) {
-  fp s;
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 12; i++) s.v[i] = subc32(t.v[i], c::P2_RAW[i], borrow, &borrow);
-  fp r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) r.v[i] = borrow ? t.v[i] : s.v[i];
-  return r;
-}
-
 // a + b < 4p < 2^383 (no carry out of limb 11), then - 2p if >= 2p.  The sum
 // and the trial subtraction run as two chains interleaved limb by limb (the
 // subtraction's limb i needs only the sum's limb i): one chain alone waits two
 // states on its carry register between links (s_nop 1 per link on gfx950),
-// two interleaved chains one.
-#ifndef CESS_ADD_ILV
-#define CESS_ADD_ILV 1
-#endif
+// two interleaved chains one.  (Against the sum's chain followed by the
+// subtraction's, here and in the Fp2 forms below: k_final 137.8 -> 136.4 ms,
+// profiles/round6_m_sweep_carry_ilv.txt, round6_n_sweep_fp2_chains.txt.)
 CESS_HD fp add(const fp& a, const fp& b) {
-#if CESS_ADD_ILV
   fp t, s;
   uint32_t carry = 0, borrow = 0;
 #pragma unroll
@@ -170,17 +156,9 @@ CESS_HD fp add(const fp& a, const fp& b) {
 #pragma unroll
   for (int i = 0; i < 12; i++) r.v[i] = borrow ? t.v[i] : s.v[i];
   return r;
-#else
-  fp t;
-  uint32_t carry = 0;
-#pragma unroll
-  for (int i = 0; i < 12; i++) t.v[i] = addc32(a.v[i], b.v[i], carry, &carry);
-  return fp_reduce2(t);
-#endif
 }
 
 CESS_HD fp sub(const fp& a, const fp& b) {
-#if CESS_ADD_ILV
   // a - b and a - b + 2p as two interleaved chains (as add), the second kept
   // if the first borrows (a - b > -2p)
   fp t, u;
@@ -194,19 +172,6 @@ CESS_HD fp sub(const fp& a, const fp& b) {
 #pragma unroll
   for (int i = 0; i < 12; i++) r.v[i] = borrow ? u.v[i] : t.v[i];
   return r;
-#else
-  fp t;
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 12; i++) t.v[i] = subc32(a.v[i], b.v[i], borrow, &borrow);
-  // if borrow: add 2p back (a - b > -2p)
-  const uint32_t mask = 0u - borrow;
-  uint32_t carry = 0;
-  fp r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) r.v[i] = addc32(t.v[i], c::P2_RAW[i] & mask, carry, &carry);
-  return r;
-#endif
 }
 
 // Unreduced sum (no conditional subtraction): a + b < 4p for a, b < 2p.
@@ -300,25 +265,10 @@ CESS_HD void opaque(uint64_t& x) { asm("" : "+v"(x)); }
 // --- 28-bit compute domain ---------------------------------------------------
 constexpr uint32_t M28 = 0x0fffffffu;
 
-// The digit mask as an operand: a literal makes every v_and_b32 an 8-byte
-// instruction; held in an SGPR (CESS_M28_SGPR, a CSE-able non-volatile asm)
-// the AND is the 4-byte VOP2 form (one wave issues 4-byte instructions every
-// 4.04 cycles against 4.53 for 8-byte ones, profiles/round5_o_lat_probe.txt).
-// Measured, not adopted: k_miller +1.7-2.1 ms, k_final +1 ms (+788
-// instructions in k_miller's step; profiles/round5_aa_sweep.txt).
-#ifndef CESS_M28_SGPR
-#define CESS_M28_SGPR 0
-#endif
-#if CESS_M28_SGPR && !defined(CESS_HOSTEMU)
-CESS_HD uint32_t m28_sgpr() {
-  uint32_t m;
-  asm("s_mov_b32 %0, 0xfffffff" : "=s"(m));
-  return m;
-}
-#define M28V m28_sgpr()
-#else
-#define M28V M28
-#endif
+// The digit mask stays a literal (an 8-byte v_and_b32).  Measured, not
+// adopted: the mask held in an SGPR, so the AND is the 4-byte VOP2 form --
+// k_miller +1.7-2.1 ms, k_final +1 ms (+788 instructions in k_miller's step;
+// profiles/round5_aa_sweep.txt).
 
 // acc += x * y (one v_mad_u64_u32; column sums stay below 2^64)
 CESS_HD void mac(uint64_t& acc, uint32_t x, uint32_t y) { acc += (uint64_t)x * y; }
@@ -330,7 +280,7 @@ CESS_HD void unpack28(const fp& a, uint32_t (&l)[14]) {
     const int off = 28 * k, i = off >> 5, sh = off & 31;
     uint32_t lo = a.v[i] >> sh;
     if (sh > 4 && i + 1 < 12) lo |= a.v[i + 1] << (32 - sh);
-    l[k] = lo & M28V;
+    l[k] = lo & M28;
   }
 }
 // 14 x 28-bit normalised limbs (value < 2^384) -> 12 x 32
@@ -349,46 +299,28 @@ CESS_HD fp pack28(const uint32_t (&l)[14]) {
 
 // Montgomery reduction tail shared by mul and sqr:
 //   columns k of the double-width product are accumulated by
-//   `col(k, h, acc)`, which adds the column's products a_i b_j with i of
-//   parity h (h = -1: all of them); the result (< 2p) is left in 14 x 28-bit
-//   digits t.
-// CESS_MONT_SEP: each column's products go to two fresh partial sums (by the
-// parity of i; the known m * p terms continue the second), and only their
-// merge, m_k and the shift stay on the carried chain -- the wave then has
-// independent mads to issue while the chain's mul_lo / and / mad / shift
-// steps complete.  A lazy Fp2 product in a dependent loop: 7,476 -> 6,524
-// cycles at one wave per SIMD, 13,085 -> 12,700 at two
-// (profiles/round5_j_fp_probe.txt, mul_sep<2,noq>).
-#ifndef CESS_MONT_SEP
-#define CESS_MONT_SEP 0
-#endif
+//   `col(k, acc)`, which adds the column's products a_i b_j; the result
+//   (< 2p) is left in 14 x 28-bit digits t.
+// Measured, not adopted: each column's products summed off the carried chain
+// in two fresh partial sums (split by the parity of i) and merged per column.
+// A lone lazy Fp2 product in a dependent loop gained (7,476 -> 6,524 cycles
+// at one wave per SIMD, profiles/round5_j_fp_probe.txt, mul_sep<2,noq>), but
+// k_miller ran 5 % slower in every region, +2 K instructions per step
+// (profiles/round5_m_diag_sep.txt).
 template <class Col>
 CESS_HD void mont28_d(Col&& col, uint32_t (&t)[14]) {
   uint32_t m[14];
   uint64_t acc = 0;
 #pragma unroll
   for (int k = 0; k < 27; k++) {
-#if CESS_MONT_SEP
-    uint64_t sa = 0, sb = 0;
-    col(k, 0, sa);
-    col(k, 1, sb);
-#pragma unroll
-    for (int i = k < 14 ? 0 : k - 13; i < (k < 14 ? k : 14); i++) mac(sb, m[i], c::P28[k - i]);
-    opaque(sa);
-    opaque(sb);
-    sa += sb;
-    opaque(sa);
-    acc += sa;
-#else
-    col(k, -1, acc);
+    col(k, acc);
 #pragma unroll
     for (int i = k < 14 ? 0 : k - 13; i < (k < 14 ? k : 14); i++) mac(acc, m[i], c::P28[k - i]);
-#endif
     if (k < 14) {
-      m[k] = ((uint32_t)acc * c::PINV28) & M28V;
+      m[k] = ((uint32_t)acc * c::PINV28) & M28;
       mac(acc, m[k], c::P28[0]);
     } else {
-      t[k - 14] = (uint32_t)acc & M28V;
+      t[k - 14] = (uint32_t)acc & M28;
     }
     acc >>= 28;
   }
@@ -402,50 +334,27 @@ CESS_HD fp mont28(Col&& col) {
 }
 
 // Two Montgomery reductions side by side (lazy Fp2 product):
-//   `col(k, h, acc0, acc1)` adds column k of each combined double-width
-//   value, products a_i b_j with i of parity h (h = -1: all); CESS_MONT_SEP
-//   as mont28_d.
+//   `col(k, acc0, acc1)` adds column k of each combined double-width value.
 template <class Col>
 CESS_HD void mont28x2(Col&& col, fp& out0, fp& out1) {
   uint32_t m0[14], m1[14], t0[14], t1[14];
   uint64_t acc0 = 0, acc1 = 0;
 #pragma unroll
   for (int k = 0; k < 27; k++) {
-#if CESS_MONT_SEP
-    uint64_t s0a = 0, s1a = 0, s0b = 0, s1b = 0;
-    col(k, 0, s0a, s1a);
-    col(k, 1, s0b, s1b);
-#pragma unroll
-    for (int i = k < 14 ? 0 : k - 13; i < (k < 14 ? k : 14); i++) {
-      mac(s0b, m0[i], c::P28[k - i]);
-      mac(s1b, m1[i], c::P28[k - i]);
-    }
-    opaque(s0a);
-    opaque(s1a);
-    opaque(s0b);
-    opaque(s1b);
-    s0a += s0b;
-    s1a += s1b;
-    opaque(s0a);
-    opaque(s1a);
-    acc0 += s0a;
-    acc1 += s1a;
-#else
-    col(k, -1, acc0, acc1);
+    col(k, acc0, acc1);
 #pragma unroll
     for (int i = k < 14 ? 0 : k - 13; i < (k < 14 ? k : 14); i++) {
       mac(acc0, m0[i], c::P28[k - i]);
       mac(acc1, m1[i], c::P28[k - i]);
     }
-#endif
     if (k < 14) {
-      m0[k] = ((uint32_t)acc0 * c::PINV28) & M28V;
-      m1[k] = ((uint32_t)acc1 * c::PINV28) & M28V;
+      m0[k] = ((uint32_t)acc0 * c::PINV28) & M28;
+      m1[k] = ((uint32_t)acc1 * c::PINV28) & M28;
       mac(acc0, m0[k], c::P28[0]);
       mac(acc1, m1[k], c::P28[0]);
     } else {
-      t0[k - 14] = (uint32_t)acc0 & M28V;
-      t1[k - 14] = (uint32_t)acc1 & M28V;
+      t0[k - 14] = (uint32_t)acc0 & M28;
+      t1[k - 14] = (uint32_t)acc1 & M28;
     }
     acc0 >>= 28;
     acc1 >>= 28;
@@ -454,66 +363,6 @@ CESS_HD void mont28x2(Col&& col, fp& out0, fp& out1) {
   t1[13] = (uint32_t)acc1;
   out0 = pack28(t0);
   out1 = pack28(t1);
-}
-
-// Four Montgomery reductions side by side (two independent lazy Fp2
-// products, mul2): four accumulation chains per column instead of two, so a
-// single wave per SIMD has independent work to issue while one chain's
-// reduction step (m = acc * p' -> m * p[0] -> shift) completes.
-template <class Col>
-CESS_HD void mont28x4(Col&& col, fp& out0, fp& out1, fp& out2, fp& out3) {
-  uint32_t m0[14], m1[14], m2[14], m3[14], t0[14], t1[14], t2[14], t3[14];
-  uint64_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-#pragma unroll
-  for (int k = 0; k < 14; k++) {
-    col(k, -1, acc0, acc1, acc2, acc3);
-#pragma unroll
-    for (int i = 0; i < k; i++) {
-      mac(acc0, m0[i], c::P28[k - i]);
-      mac(acc1, m1[i], c::P28[k - i]);
-      mac(acc2, m2[i], c::P28[k - i]);
-      mac(acc3, m3[i], c::P28[k - i]);
-    }
-    m0[k] = ((uint32_t)acc0 * c::PINV28) & M28V;
-    m1[k] = ((uint32_t)acc1 * c::PINV28) & M28V;
-    m2[k] = ((uint32_t)acc2 * c::PINV28) & M28V;
-    m3[k] = ((uint32_t)acc3 * c::PINV28) & M28V;
-    mac(acc0, m0[k], c::P28[0]);
-    mac(acc1, m1[k], c::P28[0]);
-    mac(acc2, m2[k], c::P28[0]);
-    mac(acc3, m3[k], c::P28[0]);
-    acc0 >>= 28;
-    acc1 >>= 28;
-    acc2 >>= 28;
-    acc3 >>= 28;
-  }
-#pragma unroll
-  for (int k = 14; k < 27; k++) {
-    col(k, -1, acc0, acc1, acc2, acc3);
-#pragma unroll
-    for (int i = k - 13; i < 14; i++) {
-      mac(acc0, m0[i], c::P28[k - i]);
-      mac(acc1, m1[i], c::P28[k - i]);
-      mac(acc2, m2[i], c::P28[k - i]);
-      mac(acc3, m3[i], c::P28[k - i]);
-    }
-    t0[k - 14] = (uint32_t)acc0 & M28V;
-    t1[k - 14] = (uint32_t)acc1 & M28V;
-    t2[k - 14] = (uint32_t)acc2 & M28V;
-    t3[k - 14] = (uint32_t)acc3 & M28V;
-    acc0 >>= 28;
-    acc1 >>= 28;
-    acc2 >>= 28;
-    acc3 >>= 28;
-  }
-  t0[13] = (uint32_t)acc0;
-  t1[13] = (uint32_t)acc1;
-  t2[13] = (uint32_t)acc2;
-  t3[13] = (uint32_t)acc3;
-  out0 = pack28(t0);
-  out1 = pack28(t1);
-  out2 = pack28(t2);
-  out3 = pack28(t3);
 }
 
 // a * b * 2^-392 mod p
@@ -525,10 +374,10 @@ CESS_HD fp mul(const fp& a0, const fp& b0) {
   uint32_t x[14], y[14];
   unpack28(a, x);
   unpack28(b, y);
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
+  fp r = mont28([&](int k, uint64_t& acc) {
 #pragma unroll
     for (int i = 0; i < 14; i++)
-      if (k - i >= 0 && k - i < 14 && (h < 0 || (i & 1) == h)) mac(acc, x[i], y[k - i]);
+      if (k - i >= 0 && k - i < 14) mac(acc, x[i], y[k - i]);
   });
   seq(r);
   return r;
@@ -543,13 +392,13 @@ CESS_HD fp sqr(const fp& a0) {
   unpack28(a, x);
 #pragma unroll
   for (int i = 0; i < 14; i++) x2[i] = x[i] << 1;
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
+  fp r = mont28([&](int k, uint64_t& acc) {
 #pragma unroll
     for (int i = 0; i < 14; i++) {
       const int j = k - i;
-      if (j > i && j < 14 && (h < 0 || (i & 1) == h)) mac(acc, x[i], x2[j]);
+      if (j > i && j < 14) mac(acc, x[i], x2[j]);
     }
-    if ((k & 1) == 0 && (k >> 1) < 14 && (h < 0 || ((k >> 1) & 1) == h)) mac(acc, x[k >> 1], x[k >> 1]);
+    if ((k & 1) == 0 && (k >> 1) < 14) mac(acc, x[k >> 1], x[k >> 1]);
   });
   seq(r);
   return r;
@@ -568,14 +417,16 @@ CESS_HD fp from_mont(const fp& a) {
 }
 CESS_HD fp to_mont(const fp& a_raw) { return mul(a_raw, fp_from(c::R2)); }
 
-// a^e for a fixed 12-word exponent: MSB-first sliding window of width W
-// (CESS_POW_W, default 4: decode/hash kernels 1-3 % faster than width 3 on
-// one MI355X, width 5 spills -- profiles/round4_d_sweep.txt) over the odd
-// powers a, a^3, .., a^(2^W - 1) (table held in registers; the window's entry
-// is copied under a wave-uniform branch, CESS_POW_SWITCH, not read through a
-// dynamically indexed array, so nothing goes to scratch).  For the 379-381-bit exponents used here (p-2, (p+1)/4,
-// (p-3)/4; ~229 set bits) this is ~110 multiplies instead of ~229.  All
-// branches depend on the exponent only, so they are wave-uniform.
+// a^e for a fixed 12-word exponent: MSB-first sliding window of width W = 4
+// (decode/hash kernels 1-3 % faster than width 3 on one MI355X, width 5
+// spills -- profiles/round4_d_sweep.txt) over the odd powers a, a^3, ..,
+// a^(2^W - 1) (table held in registers; the window's entry is copied under a
+// wave-uniform branch, not read through a dynamically indexed array, so
+// nothing goes to scratch; NT - 1 selects per digit instead of the branch:
+// k_hash 24.6 against 24.3 ms, profiles/round6_an_sweep_pow_switch.txt).
+// For the 379-381-bit exponents used here (p-2, (p+1)/4, (p-3)/4; ~229 set
+// bits) this is ~110 multiplies instead of ~229.  All branches depend on the
+// exponent only, so they are wave-uniform.
 // The chain runs in the 28-bit digit domain: a Montgomery product's digits
 // (< 2^28, value < 2p) are a valid operand of the next product as they are, so
 // the 12 x 32-bit pack / unpack of every multiply (~70 instructions) is paid
@@ -594,10 +445,10 @@ CESS_HD void mul_d(uint32_t (&r)[14], const uint32_t (&x)[14], const uint32_t (&
   CESS_COUNT_MUL();
   uint32_t t[14];
   mont28_d(
-      [&](int k, int h, uint64_t& acc) {
+      [&](int k, uint64_t& acc) {
 #pragma unroll
         for (int i = 0; i < 14; i++)
-          if (k - i >= 0 && k - i < 14 && (h < 0 || (i & 1) == h)) mac(acc, x[i], y[k - i]);
+          if (k - i >= 0 && k - i < 14) mac(acc, x[i], y[k - i]);
       },
       t);
 #pragma unroll
@@ -611,13 +462,13 @@ CESS_HD void sqr_d(uint32_t (&x)[14]) {
 #pragma unroll
   for (int i = 0; i < 14; i++) x2[i] = x[i] << 1;
   mont28_d(
-      [&](int k, int h, uint64_t& acc) {
+      [&](int k, uint64_t& acc) {
 #pragma unroll
         for (int i = 0; i < 14; i++) {
           const int j = k - i;
-          if (j > i && j < 14 && (h < 0 || (i & 1) == h)) mac(acc, x[i], x2[j]);
+          if (j > i && j < 14) mac(acc, x[i], x2[j]);
         }
-        if ((k & 1) == 0 && (k >> 1) < 14 && (h < 0 || ((k >> 1) & 1) == h)) mac(acc, x[k >> 1], x[k >> 1]);
+        if ((k & 1) == 0 && (k >> 1) < 14) mac(acc, x[k >> 1], x[k >> 1]);
       },
       t);
 #pragma unroll
@@ -625,14 +476,8 @@ CESS_HD void sqr_d(uint32_t (&x)[14]) {
   seq14(x);
 }
 CESS_HD uint32_t exp_bit(const uint32_t (&e)[12], int i) { return (e[i >> 5] >> (i & 31)) & 1u; }
-#ifndef CESS_POW_W
-#define CESS_POW_W 4
-#endif
-#ifndef CESS_POW_SWITCH
-#define CESS_POW_SWITCH 1
-#endif
 CESS_HD fp pow_fixed(const fp& a0, const uint32_t (&e)[12]) {
-  constexpr int W = CESS_POW_W, NT = 1 << (W - 1);   // odd powers a, a^3, .., a^(2^W - 1)
+  constexpr int W = 4, NT = 1 << (W - 1);   // odd powers a, a^3, .., a^(2^W - 1)
   fp a = a0;
   seq(a);
   uint32_t t[NT][14], a2[14], r[14], w[14];
@@ -659,7 +504,6 @@ CESS_HD fp pow_fixed(const fp& a0, const uint32_t (&e)[12]) {
       v = 2 * v + exp_bit(e, k);
       if (started) sqr_d(r);
     }
-#if CESS_POW_SWITCH
     // v is wave-uniform: a scalar branch to one copy of the table entry (14
     // moves) instead of NT - 1 selects per digit
 #if defined(CESS_HOSTEMU)
@@ -673,16 +517,6 @@ CESS_HD fp pow_fixed(const fp& a0, const uint32_t (&e)[12]) {
 #pragma unroll
         for (int q = 0; q < 14; q++) w[q] = t[m][q];
       }
-#else
-    // uniform selects (v is wave-uniform): no dynamically indexed table
-#pragma unroll
-    for (int q = 0; q < 14; q++) {
-      uint32_t x = t[0][q];
-#pragma unroll
-      for (int m = 1; m < NT; m++) x = v == (uint32_t)(2 * m + 1) ? t[m][q] : x;
-      w[q] = x;
-    }
-#endif
     if (started) {
       mul_d(r, r, w);
     } else {
@@ -907,7 +741,6 @@ CESS_HD fp2 fp2_one() { return {fp_one(), fp_zero()}; }
 CESS_HD fp2 add(const fp2& a, const fp2& b) {
   fp t0, t1, s0, s1;
   uint32_t c0 = 0, c1 = 0, b0 = 0, b1 = 0;
-#if CESS_ADD_ILV
   // the two sums and their trial subtractions: four chains, no wait states
 #pragma unroll
   for (int i = 0; i < 12; i++) {
@@ -916,18 +749,6 @@ CESS_HD fp2 add(const fp2& a, const fp2& b) {
     s0.v[i] = subc32(t0.v[i], c::P2_RAW[i], b0, &b0);
     s1.v[i] = subc32(t1.v[i], c::P2_RAW[i], b1, &b1);
   }
-#else
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    t0.v[i] = addc32(a.c0.v[i], b.c0.v[i], c0, &c0);
-    t1.v[i] = addc32(a.c1.v[i], b.c1.v[i], c1, &c1);
-  }
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    s0.v[i] = subc32(t0.v[i], c::P2_RAW[i], b0, &b0);
-    s1.v[i] = subc32(t1.v[i], c::P2_RAW[i], b1, &b1);
-  }
-#endif
   fp2 r;
 #pragma unroll
   for (int i = 0; i < 12; i++) {
@@ -937,7 +758,6 @@ CESS_HD fp2 add(const fp2& a, const fp2& b) {
   return r;
 }
 CESS_HD fp2 sub(const fp2& a, const fp2& b) {
-#if CESS_ADD_ILV
   // the two differences and the same plus 2p: four chains, no wait states
   fp t0, t1, u0, u1;
   uint32_t b0 = 0, b1 = 0, c0 = 0, c1 = 0;
@@ -955,23 +775,6 @@ CESS_HD fp2 sub(const fp2& a, const fp2& b) {
     r.c1.v[i] = b1 ? u1.v[i] : t1.v[i];
   }
   return r;
-#else
-  fp t0, t1;
-  uint32_t b0 = 0, b1 = 0, c0 = 0, c1 = 0;
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    t0.v[i] = subc32(a.c0.v[i], b.c0.v[i], b0, &b0);
-    t1.v[i] = subc32(a.c1.v[i], b.c1.v[i], b1, &b1);
-  }
-  const uint32_t m0 = 0u - b0, m1 = 0u - b1;
-  fp2 r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    r.c0.v[i] = addc32(t0.v[i], c::P2_RAW[i] & m0, c0, &c0);
-    r.c1.v[i] = addc32(t1.v[i], c::P2_RAW[i] & m1, c1, &c1);
-  }
-  return r;
-#endif
 }
 // unreduced, for mul() operands only (see add_nr(fp, fp))
 CESS_HD fp2 add_nr(const fp2& a, const fp2& b) {
@@ -1014,18 +817,6 @@ CESS_HD fp2 mul8(const fp2& a) { return {mul8(a.c0), mul8(a.c1)}; }
 
 // Inputs may be unreduced (each component < 2^384, e.g. add_nr sums): only
 // mul() and add_nr() touch them, and every output is reduced.
-#ifndef CESS_FP2_MUL_LAZY
-#define CESS_FP2_MUL_LAZY 1
-#endif
-#if !CESS_FP2_MUL_LAZY
-// Karatsuba with three separately reduced products (fewer live registers than
-// the lazy form below: for kernels that run two waves per SIMD)
-CESS_HD fp2 mul(const fp2& a, const fp2& b) {
-  fp v0 = mul(a.c0, b.c0), v1 = mul(a.c1, b.c1);
-  fp t = mul(add_nr(a.c0, a.c1), add_nr(b.c0, b.c1));
-  return {sub(v0, v1), sub(sub(t, v0), v1)};
-}
-#else
 // Lazily reduced schoolbook form: c0 = a0 b0 + a1 (K - b1) and
 // c1 = a0 b1 + a1 b0 (K = c::NEG_K28, digit-wise -b1 mod p), four
 // half-products accumulated straight into the two reduction columns -- no
@@ -1062,11 +853,11 @@ CESS_HD fp2 mul_scaled(const fp2& a, const fp2& b) {
   }
   fp2 r;
   mont28x2(
-      [&](int k, int h, uint64_t& acc0, uint64_t& acc1) {
+      [&](int k, uint64_t& acc0, uint64_t& acc1) {
 #pragma unroll
         for (int i = 0; i < 14; i++) {
           const int j = k - i;
-          if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+          if (j < 0 || j >= 14) continue;
           mac(acc0, x0[i], y0[j]);
           mac(acc1, x0[i], y1[j]);
           mac(acc0, x1[i], y1n[j]);
@@ -1079,70 +870,9 @@ CESS_HD fp2 mul_scaled(const fp2& a, const fp2& b) {
   return r;
 }
 CESS_HD fp2 mul(const fp2& a, const fp2& b) { return mul_scaled<1>(a, b); }
-// Two independent lazy products r = S a b, q = S c d in ONE column loop
-// (mont28x4): the same mads and bounds as two mul_scaled<S> calls, but four
-// accumulation chains for the wave to interleave (a lone product measured
-// 4.9 cycles per instruction at one wave per SIMD against 4.0 for dot2's
-// denser columns, profiles/round5_e_fp_probe.txt).  For kernels with the
-// register room (working set ~260 VGPRs: k_miller).
-template <uint32_t S>
-CESS_HD void mul2_scaled(const fp2& a, const fp2& b, const fp2& c, const fp2& d, fp2& r, fp2& q) {
-  static_assert(S >= 1 && S <= 3, "digit bound");
-  CESS_COUNT_MUL2();
-  CESS_COUNT_MUL2();
-  fp a0 = a.c0, a1 = a.c1, b0 = b.c0, b1 = b.c1, c0 = c.c0, c1 = c.c1, d0 = d.c0, d1 = d.c1;
-  seq(a0);
-  seq(a1);
-  seq(b0);
-  seq(b1);
-  seq(c0);
-  seq(c1);
-  seq(d0);
-  seq(d1);
-  uint32_t x0[14], x1[14], y0[14], y1[14], y1n[14], u0[14], u1[14], w0[14], w1[14], w1n[14];
-  unpack28(a0, x0);
-  unpack28(a1, x1);
-  unpack28(b0, y0);
-  unpack28(b1, y1);
-  unpack28(c0, u0);
-  unpack28(c1, u1);
-  unpack28(d0, w0);
-  unpack28(d1, w1);
-#pragma unroll
-  for (int i = 0; i < 14; i++) {
-    y1n[i] = c::NEG_K28[i] - y1[i];
-    w1n[i] = c::NEG_K28[i] - w1[i];
-    x0[i] *= S;
-    x1[i] *= S;
-    u0[i] *= S;
-    u1[i] *= S;
-  }
-  mont28x4(
-      [&](int k, int, uint64_t& acc0, uint64_t& acc1, uint64_t& acc2, uint64_t& acc3) {
-#pragma unroll
-        for (int i = 0; i < 14; i++) {
-          const int j = k - i;
-          if (j < 0 || j >= 14) continue;
-          mac(acc0, x0[i], y0[j]);
-          mac(acc1, x0[i], y1[j]);
-          mac(acc2, u0[i], w0[j]);
-          mac(acc3, u0[i], w1[j]);
-          mac(acc0, x1[i], y1n[j]);
-          mac(acc1, x1[i], y0[j]);
-          mac(acc2, u1[i], w1n[j]);
-          mac(acc3, u1[i], w0[j]);
-        }
-      },
-      r.c0, r.c1, q.c0, q.c1);
-  seq(r.c0);
-  seq(r.c1);
-  seq(q.c0);
-  seq(q.c1);
-}
-CESS_HD void mul2(const fp2& a, const fp2& b, const fp2& c, const fp2& d, fp2& r, fp2& q) {
-  mul2_scaled<1>(a, b, c, d, r, q);
-}
-#endif
+// Measured, not adopted: two independent lazy products in one column loop
+// (four accumulation chains per column for a single wave to interleave):
+// k_miller +1.6 % (profiles/round5_g_sweep.txt).
 // a*b + c*d over Fp2 with ONE Montgomery reduction per output component:
 // the schoolbook form of mul(fp2, fp2) above, 8 half-products straight into
 // the two reduction columns (columns < 14 x 2^56 x 7 + 2^36 < 2^63,
@@ -1172,11 +902,11 @@ CESS_HD fp2 dot2(const fp2& a, const fp2& b, const fp2& c, const fp2& d) {
   for (int i = 0; i < 14; i++) yb1n[i] = c::NEG_K28[i] - yb1[i], yd1n[i] = c::NEG_K28[i] - yd1[i];
   fp2 r;
   mont28x2(
-      [&](int k, int h, uint64_t& acc0, uint64_t& acc1) {
+      [&](int k, uint64_t& acc0, uint64_t& acc1) {
 #pragma unroll
         for (int i = 0; i < 14; i++) {
           const int j = k - i;
-          if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+          if (j < 0 || j >= 14) continue;
           mac(acc0, xa0[i], yb0[j]);
           mac(acc1, xa0[i], yb1[j]);
           mac(acc0, xa1[i], yb1n[j]);
@@ -1218,11 +948,11 @@ CESS_HD fp2 sqr(const fp2& a) {
   }
   fp2 r;
   mont28x2(
-      [&](int k, int h, uint64_t& acc0, uint64_t& acc1) {
+      [&](int k, uint64_t& acc0, uint64_t& acc1) {
 #pragma unroll
         for (int i = 0; i < 14; i++) {
           const int j = k - i;
-          if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+          if (j < 0 || j >= 14) continue;
           mac(acc0, s[i], d[j]);
           mac(acc1, x0[i], x1d[j]);
         }
@@ -1295,21 +1025,7 @@ CESS_HD fp6 mul_v(const fp6& a) { return {mul_nr(a.c2), a.c0, a.c1}; }
 // unreduced, for mul() operands only
 CESS_HD fp6 add_nr(const fp6& a, const fp6& b) { return {add_nr(a.c0, b.c0), add_nr(a.c1, b.c1), add_nr(a.c2, b.c2)}; }
 
-#ifndef CESS_MUL2
-#define CESS_MUL2 0
-#endif
 CESS_HD fp6 mul(const fp6& a, const fp6& b) {
-#if CESS_MUL2
-  // the six Karatsuba products as three independent pairs (mul2)
-  fp2 t0, t1, t2, u0, u1, u2;
-  mul2(a.c0, b.c0, a.c1, b.c1, t0, t1);
-  mul2(a.c2, b.c2, add_nr(a.c1, a.c2), add_nr(b.c1, b.c2), t2, u0);
-  mul2(add_nr(a.c0, a.c1), add_nr(b.c0, b.c1), add_nr(a.c0, a.c2), add_nr(b.c0, b.c2), u1, u2);
-  fp2 c0 = add(mul_nr(sub(sub(u0, t1), t2)), t0);
-  fp2 c1 = add(sub(sub(u1, t0), t1), mul_nr(t2));
-  fp2 c2 = add(sub(sub(u2, t0), t2), t1);
-  return {c0, c1, c2};
-#else
   fp2 t0 = mul(a.c0, b.c0);
   fp2 t1 = mul(a.c1, b.c1);
   fp2 t2 = mul(a.c2, b.c2);
@@ -1318,7 +1034,6 @@ CESS_HD fp6 mul(const fp6& a, const fp6& b) {
   fp2 c1 = add(sub(sub(mul(add_nr(a.c0, a.c1), add_nr(b.c0, b.c1)), t0), t1), mul_nr(t2));
   fp2 c2 = add(sub(sub(mul(add_nr(a.c0, a.c2), add_nr(b.c0, b.c2)), t0), t2), t1);
   return {c0, c1, c2};
-#endif
 }
 CESS_HD fp6 sqr(const fp6& a) {
   // CH-SQR2
@@ -1345,13 +1060,7 @@ CESS_HD fp6 mul_by_01(const fp6& a, const fp2& b0, const fp2& b1) {
 }
 // a * (b1 v)
 CESS_HD fp6 mul_by_1(const fp6& a, const fp2& b1) {
-#if CESS_MUL2
-  fp2 p2, p0;
-  mul2(a.c2, b1, a.c0, b1, p2, p0);
-  return {mul_nr(p2), p0, mul(a.c1, b1)};
-#else
   return {mul_nr(mul(a.c2, b1)), mul(a.c0, b1), mul(a.c1, b1)};
-#endif
 }
 CESS_HD fp6 inv(const fp6& a) {
   fp2 c0 = sub(sqr(a.c0), mul_nr(mul(a.c1, a.c2)));

@@ -316,7 +316,7 @@ CESS_HD g1a hash_to_g1(const uint8_t* msg, uint32_t len) {
 
 #if !defined(CESS_HOSTEMU)
 // hash_to_g1 with the values that wait across an SSWU exponentiation parked
-// in LDS (k_hash, CESS_HASH_PARK): the second field element u1 while the
+// in LDS (k_hash): the second field element u1 while the
 // first is mapped, and the first image Q0 while the second is mapped -- 48
 // dwords that otherwise stay in VGPRs beside the window-4 power table and
 // make k_hash spill (76 VGPRs, 304 B/lane).  park: 48 rows x 256 lanes, row r

@@ -150,11 +150,11 @@ CESS_HD fph pmul_scaled(const fph& a0, const fph& b0) {
   seq(b);
   uint32_t xa[14], xb[14], ya[14], yb[14];
   pair_digits<S>(a, b, xa, xb, ya, yb);
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
+  fp r = mont28([&](int k, uint64_t& acc) {
 #pragma unroll
     for (int i = 0; i < 14; i++) {
       const int j = k - i;
-      if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+      if (j < 0 || j >= 14) continue;
       mac(acc, xa[i], ya[j]);
       mac(acc, xb[i], yb[j]);
     }
@@ -201,11 +201,11 @@ CESS_HD fph pdot2(const fph& a0, const fph& b0, const fph& c0, const fph& d0) {
   uint32_t xa[14], xb[14], ya[14], yb[14], ua[14], ub[14], wa[14], wb[14];
   pair_digits(a, b, xa, xb, ya, yb);
   pair_digits(c, d, ua, ub, wa, wb);
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
+  fp r = mont28([&](int k, uint64_t& acc) {
 #pragma unroll
     for (int i = 0; i < 14; i++) {
       const int j = k - i;
-      if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+      if (j < 0 || j >= 14) continue;
       mac(acc, xa[i], ya[j]);
       mac(acc, xb[i], yb[j]);
       mac(acc, ua[i], wa[j]);
@@ -253,11 +253,11 @@ CESS_HD pyd prep_y(const fph& y0) {
 // pmul / pdot2)
 CESS_HD fph pmul_p(const pxd& x, const pyd& y) {
   CESS_COUNT_MUL2();
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
+  fp r = mont28([&](int k, uint64_t& acc) {
 #pragma unroll
     for (int i = 0; i < 14; i++) {
       const int j = k - i;
-      if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+      if (j < 0 || j >= 14) continue;
       mac(acc, x.a[i], y.a[j]);
       mac(acc, x.b[i], y.b[j]);
     }
@@ -267,38 +267,15 @@ CESS_HD fph pmul_p(const pxd& x, const pyd& y) {
 }
 CESS_HD fph pdot2_p(const pxd& x, const pyd& y, const pxd& u, const pyd& w) {
   CESS_COUNT_HALVES(8);
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
+  fp r = mont28([&](int k, uint64_t& acc) {
 #pragma unroll
     for (int i = 0; i < 14; i++) {
       const int j = k - i;
-      if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
+      if (j < 0 || j >= 14) continue;
       mac(acc, x.a[i], y.a[j]);
       mac(acc, x.b[i], y.b[j]);
       mac(acc, u.a[i], w.a[j]);
       mac(acc, u.b[i], w.b[j]);
-    }
-  });
-  seq(r);
-  return {r};
-}
-
-// this lane's component of x y + u w + s t from prepared operands: ONE
-// reduction over six half-products.  Columns < 3 x 14 x (2^56 + 2^57) + 14 x
-// 2^56 < 2^63.2 (x digits < 2^28, y digits < 2^29: K - b1), and the value
-// < 3 x 8p x 2^385 < p R for inputs < 8p, so the reduction returns < 2p.
-CESS_HD fph pdot3_p(const pxd& x, const pyd& y, const pxd& u, const pyd& w, const pxd& s, const pyd& t) {
-  CESS_COUNT_HALVES(12);
-  fp r = mont28([&](int k, int h, uint64_t& acc) {
-#pragma unroll
-    for (int i = 0; i < 14; i++) {
-      const int j = k - i;
-      if (j < 0 || j >= 14 || (h >= 0 && (i & 1) != h)) continue;
-      mac(acc, x.a[i], y.a[j]);
-      mac(acc, x.b[i], y.b[j]);
-      mac(acc, u.a[i], w.a[j]);
-      mac(acc, u.b[i], w.b[j]);
-      mac(acc, s.a[i], t.a[j]);
-      mac(acc, s.b[i], t.b[j]);
     }
   });
   seq(r);
@@ -317,46 +294,13 @@ CESS_HD fp6h add_nr(const fp6h& a, const fp6h& b) {
 }
 CESS_HD fp6h mul_v(const fp6h& a) { return {mul_nr(a.c2), a.c0, a.c1}; }
 
-// Schoolbook Fp6 product as three lazily reduced dot products (one reduction
-// per output component; v^3 = xi):
-//   c0 = a0 b0 + a1 (xi b2) + a2 (xi b1),  c1 = a0 b1 + a1 b0 + a2 (xi b2),
-//   c2 = a0 b2 + a1 b1 + a2 b0.
-// 17 % more mads than Karatsuba's six products, but the three x operands and
-// five y operands are prepared once (unpack + DPP exchange) and there are no
-// operand sums, no re-preparation of them and no recombination: fewer VALU
-// instructions per Fp6 product (CESS_PAIR_SB).  a(j): this lane's component of
-// a's coefficient j (a loader or register values), < 8p; b's coefficients < 4p.
-// Measured, not adopted: static VALU -2.5 % (k_miller2) / -2.9 % (k_final2),
-// but 15 / 62 spilled VGPRs, and equal time on the same box (k_miller2
-// 126.8-126.9 vs 126.7-127.0, k_final2 140.8-141.9 vs 140.9-141.0 ms,
-// profiles/round6_k_sweep_schoolbook.txt).
-#ifndef CESS_PAIR_SB
-#define CESS_PAIR_SB 0
-#endif
-template <class LA>
-CESS_HD fp6h pmul6_sb(LA&& a, const fp6h& b) {
-  const pxd x0 = prep_x(a(0)), x1 = prep_x(a(1)), x2 = prep_x(a(2));
-  fp6h c;
-  {
-    const pyd y0 = prep_y(b.c0), y1 = prep_y(b.c1);
-    c.c2 = pdot3_p(x0, prep_y(b.c2), x1, y1, x2, y0);
-    CESS_MEMBAR();
-    // xi b2, xi b1 from b reduced below 2p: callers pass unreduced sums (< 4p:
-    // add_nr(a0, v a1) in the squaring, g0 + g1 in FE_MUL), and xi's 2p - b
-    // on the even lane needs b < 2p
-    const pyd xy2 = prep_y(mul_nr_nr(fph{fp_reduce2(b.c2.v)}));
-    c.c1 = pdot3_p(x0, y1, x1, y0, x2, xy2);
-    CESS_MEMBAR();
-    c.c0 = pdot3_p(x0, y0, x1, xy2, x2, prep_y(mul_nr_nr(fph{fp_reduce2(b.c1.v)})));
-  }
-  return c;
-}
-
-// Karatsuba Fp6 product (as field.hpp mul(fp6, fp6))
+// Karatsuba Fp6 product (as field.hpp mul(fp6, fp6)).  Measured, not adopted:
+// the schoolbook product as three lazily reduced dot products of three terms
+// (one reduction per output component, operands prepared once): static VALU
+// -2.5 % (k_miller2) / -2.9 % (k_final2), but 15 / 62 spilled VGPRs, and
+// equal time on the same box (k_miller2 126.8-126.9 vs 126.7-127.0, k_final2
+// 140.8-141.9 vs 140.9-141.0 ms, profiles/round6_k_sweep_schoolbook.txt).
 CESS_HD fp6h pmul6(const fp6h& a, const fp6h& b) {
-#if CESS_PAIR_SB
-  return pmul6_sb([&](int j) { return j == 0 ? a.c0 : j == 1 ? a.c1 : a.c2; }, b);
-#endif
   const fph t0 = pmul(a.c0, b.c0);
   const fph t1 = pmul(a.c1, b.c1);
   const fph t2 = pmul(a.c2, b.c2);
@@ -366,24 +310,13 @@ CESS_HD fp6h pmul6(const fp6h& a, const fp6h& b) {
   return {c0, c1, c2};
 }
 // a * (b1 v)
-#ifndef CESS_PAIR_PREP
-#define CESS_PAIR_PREP 1
-#endif
 CESS_HD fp6h pmul_by_1(const fp6h& a, const fph& b1) {
-#if CESS_PAIR_PREP
   const pyd y = prep_y(b1);   // shared by the three products
   const fph p2 = pmul_p(prep_x(a.c2), y);
   CESS_MEMBAR();
   const fph p0 = pmul_p(prep_x(a.c0), y);
   CESS_MEMBAR();
   return {mul_nr(p2), p0, pmul_p(prep_x(a.c1), y)};
-#else
-  const fph p2 = pmul(a.c2, b1);
-  CESS_MEMBAR();
-  const fph p0 = pmul(a.c0, b1);
-  CESS_MEMBAR();
-  return {mul_nr(p2), p0, pmul(a.c1, b1)};
-#endif
 }
 
 // One signature's Fp12 in the lane pair's LDS image G[18][CESS_PAIR_THREADS]: lane t owns
@@ -422,19 +355,17 @@ CESS_HD void pst6(const S& s, int h, const fp6h& a) {
 }
 
 // f <- f^2 (complex squaring: 2 Fp6 products), staged.hpp sqr12
-// CESS_PAIR_LOOP (bit mask): the Miller step's repeated Fp6 products as
-// two-iteration loops over ONE inlined product body each -- bit 1 psqr12's two
-// pmul6, bit 2 pmul014's two mul_by_01 halves, bit 4 pmul014_one's -- a
-// smaller step body for the instruction cache (staged.hpp CESS_MUL014_LOOP
-// for k_miller_rr).  Default 5: k_miller2 31.6 K -> 23.7 K instructions,
-// 120.0-120.4 -> 119.5 ms same box (profiles/round6_ab_sweep_loop.txt); bit
-// 2 spills 27 VGPRs (the loop-carried u beside the dot products' operands).
-#ifndef CESS_PAIR_LOOP
-#define CESS_PAIR_LOOP 5
-#endif
+// The Miller step's repeated Fp6 products run as two-iteration loops over ONE
+// inlined product body each -- psqr12's two pmul6 and pmul014_one's two
+// halves -- a smaller step body for the instruction cache (staged.hpp
+// CESS_MUL014_LOOP for k_miller_rr): k_miller2 31.6 K -> 23.7 K instructions,
+// 120.0-120.4 -> 119.5 ms same box (profiles/round6_ab_sweep_loop.txt).
+// pmul014 stays unrolled: its two mul_by_01 halves as a loop spill 27 VGPRs
+// (the loop-carried u beside the dot products' operands), and the spill-free
+// form with bb made inside the first iteration measured equal
+// (profiles/round6_ae_sweep_loop7.txt).
 template <class S>
 CESS_HD void psqr12(const S& f) {
-#if CESS_PAIR_LOOP & 1
   fp6h ab;
 #pragma unroll 1
   for (int it = 0; it < 2; it++) {
@@ -453,27 +384,11 @@ CESS_HD void psqr12(const S& f) {
       pst6(f, 1, dbl(ab));
     }
   }
-#else
-  fp6h ab;
-  {
-    const fp6h a0 = pld6(f, 0), a1 = pld6(f, 1);
-    ab = pmul6(a0, a1);
-  }
-  CESS_MEMBAR();
-  fp6h x;
-  {
-    const fp6h a0 = pld6(f, 0), a1 = pld6(f, 1);
-    x = pmul6(add_nr(a0, a1), add_nr(a0, mul_v(a1)));
-  }
-  pst6(f, 0, sub(sub(x, ab), mul_v(ab)));
-  pst6(f, 1, dbl(ab));
-#endif
 }
 
 // a * (b0 + b1 v) for the Fp6 in store half h, as staged.hpp mul_by_01_dot
 template <class S>
 CESS_HD fp6h pmul_by_01_dot(const S& f, int h, const fph& b0, const fph& b1, const fph& xb1) {
-#if CESS_PAIR_PREP
   // b0 enters all three dot products, b1 two, each coefficient of f two
   const pyd y0 = prep_y(b0);
   fp6h r;
@@ -486,15 +401,6 @@ CESS_HD fp6h pmul_by_01_dot(const S& f, int h, const fph& b0, const fph& b1, con
   CESS_MEMBAR();
   r.c2 = pdot2_p(prep_x(f.ld(3 * h + 1)), prep_y(b1), prep_x(f.ld(3 * h + 2)), y0);
   return r;
-#else
-  fp6h r;
-  r.c0 = pdot2(f.ld(3 * h), b0, f.ld(3 * h + 2), xb1);
-  CESS_MEMBAR();
-  r.c1 = pdot2(f.ld(3 * h), b1, f.ld(3 * h + 1), b0);
-  CESS_MEMBAR();
-  r.c2 = pdot2(f.ld(3 * h + 1), b1, f.ld(3 * h + 2), b0);
-  return r;
-#endif
 }
 
 // f <- f * (c0 + c1 v + c4 v w), staged.hpp mul014
@@ -502,26 +408,6 @@ template <class S>
 CESS_HD void pmul014(const S& f, const fph& c0, const fph& c1, const fph& c4) {
   const fp6h bb = pmul_by_1(pld6(f, 1), c4);
   CESS_MEMBAR();
-#if CESS_PAIR_LOOP & 2
-  {
-    fp6h u;
-    const fph d = add(c1, c4);
-#pragma unroll 1
-    for (int it = 0; it < 2; it++) {
-      const fph b1 = it ? d : c1;
-      const fp6h r = pmul_by_01_dot(f, it, c0, b1, mul_nr_nr(b1));
-      CESS_MEMBAR();
-      if (it == 0) {
-        pst6(f, 1, add(pld6(f, 0), pld6(f, 1)));   // f.c1 <- a0 + a1 (read by it = 1)
-        pst6(f, 0, add(mul_v(bb), r));
-        u = add(r, bb);
-      } else {
-        pst6(f, 1, sub(r, u));
-      }
-    }
-    return;
-  }
-#endif
   const fp6h aa = pmul_by_01_dot(f, 0, c0, c1, mul_nr_nr(c1));
   CESS_MEMBAR();
   pst6(f, 1, add(pld6(f, 0), pld6(f, 1)));   // f.c1 <- a0 + a1 (consumed below)
@@ -535,20 +421,12 @@ CESS_HD void pmul014(const S& f, const fph& c0, const fph& c1, const fph& c4) {
 
 // a * (1 + b1 v)
 CESS_HD fp6h pmul_by_01_one(const fp6h& a, const fph& b1) {
-#if CESS_PAIR_PREP
   const pyd y = prep_y(b1);   // shared by the three products
   const fph p2 = pmul_p(prep_x(a.c2), y);
   CESS_MEMBAR();
   const fph p0 = pmul_p(prep_x(a.c0), y);
   CESS_MEMBAR();
   return {add(a.c0, mul_nr(p2)), add(a.c1, p0), add(a.c2, pmul_p(prep_x(a.c1), y))};
-#else
-  const fph p2 = pmul(a.c2, b1);
-  CESS_MEMBAR();
-  const fph p0 = pmul(a.c0, b1);
-  CESS_MEMBAR();
-  return {add(a.c0, mul_nr(p2)), add(a.c1, p0), add(a.c2, pmul(a.c1, b1))};
-#endif
 }
 
 // f <- f * (1 + c1 v + c4 v w), staged.hpp mul014_one
@@ -556,33 +434,20 @@ template <class S>
 CESS_HD void pmul014_one(const S& f, const fph& c1, const fph& c4) {
   const fp6h bb = pmul_by_1(pld6(f, 1), c4);
   CESS_MEMBAR();
-#if CESS_PAIR_LOOP & 4
-  {
-    fp6h u;
-    const fph d = add(c1, c4);
+  fp6h u;
+  const fph d = add(c1, c4);
 #pragma unroll 1
-    for (int it = 0; it < 2; it++) {
-      const fp6h r = pmul_by_01_one(pld6(f, it), it ? d : c1);
-      CESS_MEMBAR();
-      if (it == 0) {
-        pst6(f, 1, add(pld6(f, 0), pld6(f, 1)));
-        pst6(f, 0, add(mul_v(bb), r));
-        u = add(r, bb);
-      } else {
-        pst6(f, 1, sub(r, u));
-      }
+  for (int it = 0; it < 2; it++) {
+    const fp6h r = pmul_by_01_one(pld6(f, it), it ? d : c1);
+    CESS_MEMBAR();
+    if (it == 0) {
+      pst6(f, 1, add(pld6(f, 0), pld6(f, 1)));   // f.c1 <- a0 + a1 (read by it = 1)
+      pst6(f, 0, add(mul_v(bb), r));
+      u = add(r, bb);
+    } else {
+      pst6(f, 1, sub(r, u));
     }
-    return;
   }
-#endif
-  const fp6h aa = pmul_by_01_one(pld6(f, 0), c1);
-  CESS_MEMBAR();
-  pst6(f, 1, add(pld6(f, 0), pld6(f, 1)));
-  pst6(f, 0, add(mul_v(bb), aa));
-  const fp6h u = add(aa, bb);
-  CESS_MEMBAR();
-  const fp6h t = pmul_by_01_one(pld6(f, 1), add(c1, c4));
-  pst6(f, 1, sub(t, u));
 }
 
 // The two-pair Miller loop of staged.hpp miller_loop2_staged over a lane

@@ -100,9 +100,6 @@ CESS_HD bool pis_conj12(const A& a, const B& b) {
 // the second held in registers
 template <class LA>
 CESS_HD fp6h pmul6_lr(LA&& a, const fp6h& b) {
-#if CESS_PAIR_SB
-  return pmul6_sb(a, b);
-#endif
   const fph v0 = pmul(a(0), b.c0);
   CESS_MEMBAR();
   const fph v1 = pmul(a(1), b.c1);
@@ -121,16 +118,12 @@ CESS_HD fp6h pmul6_lr(LA&& a, const fp6h& b) {
 // ordered so that at most one Fp6 product is held: t0 = f0 g0;
 // x = (f0 + f1)(g0 + g1); f0 <- x - t0 (f0 is dead: t1 needs f1 only);
 // t1 = f1 g1; f1 <- f0 - t1 = f0 g1 + f1 g0; f0 <- t0 + v t1.
-// CESS_PAIR_FE_LOOP (default 1): the three Fp6 products as a three-iteration
-// loop over ONE inlined pmul6_lr body (a third of the code, as pair.hpp
-// CESS_PAIR_LOOP): k_final2 98.3 K -> 87.3 K instructions, 129.6-129.9 ->
-// 129.1 ms same box (profiles/round6_ac_sweep_feloop.txt)
-#ifndef CESS_PAIR_FE_LOOP
-#define CESS_PAIR_FE_LOOP 1
-#endif
+// The three Fp6 products run as a three-iteration loop over ONE inlined
+// pmul6_lr body (a third of the code, as pair.hpp psqr12): k_final2 98.3 K ->
+// 87.3 K instructions, 129.6-129.9 -> 129.1 ms same box against the unrolled
+// form (profiles/round6_ac_sweep_feloop.txt)
 template <class S, class G>
 CESS_HD void pmul12(const S& f, const G& g) {
-#if CESS_PAIR_FE_LOOP
   fp6h t0;
 #pragma unroll 1
   for (int it = 0; it < 3; it++) {
@@ -158,33 +151,6 @@ CESS_HD void pmul12(const S& f, const G& g) {
       pst6(f, 0, add(t0, mul_v(r)));
     }
   }
-#else
-  fp6h t0;
-  {
-    const fp6h g0 = pld6(g, 0);
-    t0 = pmul6_lr([&](int j) { return f.ld(j); }, g0);
-  }
-  CESS_MEMBAR();
-  {
-    fp6h gs;
-    {
-      const fp6h g0 = pld6(g, 0), g1 = pld6(g, 1);
-      gs = add_nr(g0, g1);
-    }
-    const fp6h x = pmul6_lr([&](int j) { return add_nr(f.ld(j), f.ld(3 + j)); }, gs);
-    CESS_MEMBAR();
-    pst6(f, 0, sub(x, t0));
-  }
-  CESS_MEMBAR();
-  fp6h t1;
-  {
-    const fp6h g1 = pld6(g, 1);
-    t1 = pmul6_lr([&](int j) { return f.ld(3 + j); }, g1);
-  }
-  CESS_MEMBAR();
-  pst6(f, 1, sub(pld6(f, 0), t1));
-  pst6(f, 0, add(t0, mul_v(t1)));
-#endif
 }
 
 // Fp6 square of the store half h (a pmul6 of the half with itself)
@@ -290,38 +256,11 @@ CESS_HD void pcyc_square_run(const S& f, int n) {
   for (int k = 0; k < 6; k++) f.st(k, z[k]);
 }
 
-// n Karabina compressed squarings (staged.hpp kcyc_run) of (z2, z3, z4, z5),
-// all in registers
-CESS_HD void pkcyc_run(fph& z2, fph& z3, fph& z4, fph& z5, int n) {
-#pragma unroll 1
-  for (int r = 0; r < n; r++) {
-    CESS_MEMBAR();
-    fph u, v;
-    {
-      const fph b3 = pmul_scaled<3>(z4, z5);
-      CESS_MEMBAR();
-      const fph t3 = pmul_scaled<3>(add_nr(z4, z5), add_xi_nr(z4, z5));
-      const fph nb3 = mul_nr(b3);
-      u = sub(sub(t3, b3), nb3);   // 3 (z4^2 + xi z5^2)
-      v = dbl(nb3);                // 6 xi z4 z5
-    }
-    CESS_MEMBAR();
-    {
-      const fph b3 = pmul_scaled<3>(z2, z3);
-      CESS_MEMBAR();
-      const fph t3 = pmul_scaled<3>(add_nr(z2, z3), add_xi_nr(z2, z3));
-      z4 = sub(sub(sub(t3, b3), mul_nr(b3)), dbl(z4));
-      z5 = dbl(add(z5, b3));
-    }
-    CESS_MEMBAR();
-    z2 = add(dbl(z2), v);
-    z3 = sub(u, dbl(z3));
-  }
-}
-
 CESS_HD fp2 xchg2(const fp2& a) { return {xchg(a.c0), xchg(a.c1)}; }
 
-// n Karabina compressed squarings split by PRODUCTS over the pair: the
+// n Karabina compressed squarings (staged.hpp kcyc_run) split by PRODUCTS over
+// the pair (k_final 139.0 -> 137.0-137.2 ms against the split by components
+// with a pmul_scaled<3> per product, profiles/round6_g_sweep.txt): the
 // squaring's two halves are independent -- (z4, z5) gives 3 (z4^2 + xi z5^2)
 // and 6 xi z4 z5, which update z3 and z2; (z2, z3) gives 3 (z2^2 + xi z3^2)
 // and 6 z2 z3, which update z4 and z5 -- so each lane holds one half as FULL
@@ -396,10 +335,6 @@ CESS_HD fph pcyc_z0(const fph& z1, const fph& z2, const fph& z3, const fph& z4, 
 template <class B, class XFn>
 CESS_HD void pcyc_chain(const B& base, XFn&& X) {
   constexpr int ND = 3;   // decompressed powers
-#ifndef CESS_PAIR_KCYC_PS
-#define CESS_PAIR_KCYC_PS 1
-#endif
-#if CESS_PAIR_KCYC_PS
   {
     // store indices of (u, w): lane 0 (z4, z5) = (1, 5), lane 1 (z3, z2) = (2, 3)
     const bool hi = pair_hi_mask() != 0;
@@ -417,24 +352,6 @@ CESS_HD void pcyc_chain(const B& base, XFn&& X) {
       x.st_full(kw, w);
     }
   }
-#else
-  {
-    fph z4 = base.ld(1), z5 = base.ld(5), z2 = base.ld(3), z3 = base.ld(2);
-    int k = 0;
-#pragma unroll 1
-    for (int j = 0; j < ND; j++) {
-      const int stop = j == 0 ? 16 : j == 1 ? 48 : 57;
-      pkcyc_run(z2, z3, z4, z5, stop - k);
-      k = stop;
-      CESS_MEMBAR();
-      const auto x = X(j);
-      x.st(3, z2);
-      x.st(2, z3);
-      x.st(1, z4);
-      x.st(5, z5);
-    }
-  }
-#endif
   CESS_MEMBAR();
   bool degen = false;
   fph prod = fph_one();

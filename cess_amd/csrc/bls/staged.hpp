@@ -180,43 +180,13 @@ CESS_HD bool is_conj12(const A& a, const B& b) {
   return r;
 }
 
-#ifndef CESS_SQR12_LOOP
-#define CESS_SQR12_LOOP 0
-#endif
-#ifndef CESS_MUL014_LOOP
-#define CESS_MUL014_LOOP 0
-#endif
-// f <- f^2  (complex squaring: 2 Fp6 multiplies)
+// f <- f^2  (complex squaring: 2 Fp6 multiplies).  Measured, not adopted: the
+// two products as a two-pass loop over one copy of the code (half the
+// instruction bytes): k_miller 152.94 against 152.61 ms, its step body stays
+// far larger than the instruction cache either way
+// (profiles/round5_d_sweep.txt).
 template <class S>
 CESS_HD void sqr12(const S& f) {
-#if CESS_SQR12_LOOP
-  // the two Fp6 products share ONE copy of the code (a two-pass loop over
-  // operands chosen per pass): half the instruction bytes of the squaring, so
-  // more of k_miller's step body stays in the instruction cache
-  fp6 ab;
-#pragma unroll 1
-  for (int it = 0; it < 2; it++) {
-    fp6 x, y;
-    {
-      const fp6 a0 = ld6(f, 0), a1 = ld6(f, 1);
-      if (it) {
-        x = add_nr(a0, a1);
-        y = add_nr(a0, mul_v(a1));
-      } else {
-        x = a0;
-        y = a1;
-      }
-    }
-    const fp6 r = mul(x, y);
-    CESS_MEMBAR();
-    if (it) {
-      st6(f, 0, sub(sub(r, ab), mul_v(ab)));
-      st6(f, 1, dbl(ab));
-    } else {
-      ab = r;
-    }
-  }
-#else
   fp6 ab;
   {
     fp6 a0 = ld6(f, 0), a1 = ld6(f, 1);
@@ -230,7 +200,6 @@ CESS_HD void sqr12(const S& f) {
   }
   st6(f, 0, sub(sub(x, ab), mul_v(ab)));
   st6(f, 1, dbl(ab));
-#endif
 }
 
 // a * (b0 + b1 v) for an Fp6 `a` in store half h (coefficients fetched per
@@ -250,6 +219,11 @@ CESS_HD fp6 mul_by_01_dot(const S& f, int h, const fp2& b0, const fp2& b1, const
   return r;
 }
 
+// CESS_MUL014_LOOP: mul014 / mul014_one as two-pass loops over one copy of
+// their Fp6 product (the Makefile sets it for k_pairing_rr.o)
+#ifndef CESS_MUL014_LOOP
+#define CESS_MUL014_LOOP 0
+#endif
 // f <- f * (c0 + c1 v + c4 v w)   (bls12_381 Fp12::mul_by_014, in place)
 template <class S>
 CESS_HD void mul014(const S& f, const fp2& c0, const fp2& c1, const fp2& c4) {
@@ -297,13 +271,7 @@ CESS_HD void mul014(const S& f, const fp2& c0, const fp2& c1, const fp2& c4) {
 
 // a * (1 + b1 v): mul_by_01 with b0 = 1 (a reduced)
 CESS_HD fp6 mul_by_01_one(const fp6& a, const fp2& b1) {
-#if CESS_MUL2
-  fp2 p2, p0;
-  mul2(a.c2, b1, a.c0, b1, p2, p0);
-  return {add(a.c0, mul_nr(p2)), add(a.c1, p0), add(a.c2, mul(a.c1, b1))};
-#else
   return {add(a.c0, mul_nr(mul(a.c2, b1))), add(a.c1, mul(a.c0, b1)), add(a.c2, mul(a.c1, b1))};
-#endif
 }
 
 // f <- f * (1 + c1 v + c4 v w): mul014 for a line normalised to c0 = 1
@@ -367,32 +335,17 @@ CESS_HD void mul12(const S& f, const G& g) {
 // fp6) keeps both 72-dword operands live as well, which spills at two waves
 // per SIMD.  Loaders may return unreduced sums (< 4p); sums of two of them
 // (< 8p) still satisfy mul()'s input bound.
-// CESS_FE_PF (measurement variant): the next diagonal product's operands are
-// loaded before the current product, so their HBM latency overlaps its mads
-// (48 more live VGPRs).
-#ifndef CESS_FE_PF
-#define CESS_FE_PF 0
-#endif
+// Measured, not adopted: loading the next diagonal product's operands before
+// the current product (48 more live VGPRs): k_final 1 ms slower
+// (profiles/round5_u_sweep_fepf.txt).
 template <class LA, class LB, class SK>
 CESS_HD void mul6_stream(LA&& a, LB&& b, SK&& sink) {
-#if CESS_FE_PF
-  fp2 pa = a(0), pb = b(0);
-  fp2 qa = a(1), qb = b(1);
-  const fp2 v0 = mul(pa, pb);
-  CESS_MEMBAR();
-  pa = a(2), pb = b(2);
-  const fp2 v1 = mul(qa, qb);
-  CESS_MEMBAR();
-  const fp2 v2 = mul(pa, pb);
-  CESS_MEMBAR();
-#else
   const fp2 v0 = mul(a(0), b(0));
   CESS_MEMBAR();
   const fp2 v1 = mul(a(1), b(1));
   CESS_MEMBAR();
   const fp2 v2 = mul(a(2), b(2));
   CESS_MEMBAR();
-#endif
   sink(0, add(mul_nr(sub(sub(mul(add_nr(a(1), a(2)), add_nr(b(1), b(2))), v1), v2)), v0));
   CESS_MEMBAR();
   sink(1, add(sub(sub(mul(add_nr(a(0), a(1)), add_nr(b(0), b(1))), v0), v1), mul_nr(v2)));
@@ -403,35 +356,17 @@ CESS_HD void mul6_stream(LA&& a, LB&& b, SK&& sink) {
 
 // d <- f * g (Karatsuba over Fp6) with every operand streamed: d must be a
 // store distinct from f and g; t is a one-Fp6 temporary store (3 Fp2, indices
-// 0-2).  t0 = f0 g0 goes to t, t1 = f1 g1 to d.c1, then d.c0 = t0 + v t1 and
-// d.c1 = (f0 + f1)(g0 + g1) - t0 - t1 in place.  (Parking the diagonal products
-// in an HBM slot instead of registers measured slower: k_final 186 vs 173 ms
-// per 1 M, profiles/r02q_sweep.txt.)
-template <class D, class S, class G, class T>
-CESS_HD void mul12_stream(const D& d, const S& f, const G& g, const T& t) {
-  mul6_stream([&](int j) { return f.ld(j); }, [&](int j) { return g.ld(j); },
-              [&](int j, const fp2& v) { t.st(j, v); });
-  mul6_stream([&](int j) { return f.ld(3 + j); }, [&](int j) { return g.ld(3 + j); },
-              [&](int j, const fp2& v) { d.st(3 + j, v); });
-  d.st(0, add(t.ld(0), mul_nr(d.ld(5))));
-  d.st(1, add(t.ld(1), d.ld(3)));
-  d.st(2, add(t.ld(2), d.ld(4)));
-  CESS_MEMBAR();
-  mul6_stream([&](int j) { return add_nr(f.ld(j), f.ld(3 + j)); },
-              [&](int j) { return add_nr(g.ld(j), g.ld(3 + j)); },
-              [&](int j, const fp2& x) { d.st(3 + j, sub(sub(x, t.ld(j)), d.ld(3 + j))); });
-}
-
-// mul12_stream with the park `pk` (3 Fp2, LDS) caching each Fp6 product's
-// FIRST operand (f0, f1, then f0 + f1) instead of holding the temporary t0
-// (now the store `t`, an HBM slot): every a(j) of mul6_stream is an LDS read,
-// so f is read from HBM 12 times (Fp2) per product instead of 36 -- 60 Fp2
-// loads + 12 stores against 78 + 9 (k_final's HBM traffic is its clock:
+// 0-2, an HBM slot).  t0 = f0 g0 goes to t, t1 = f1 g1 to d.c1, then
+// d.c0 = t0 + v t1 and d.c1 = (f0 + f1)(g0 + g1) - t0 - t1 in place.  (Parking
+// the diagonal products in an HBM slot instead of registers measured slower:
+// k_final 186 vs 173 ms per 1 M, profiles/r02q_sweep.txt.)
+// The park `pk` (3 Fp2, LDS) caches each Fp6 product's FIRST operand (f0, f1,
+// then f0 + f1): every a(j) of mul6_stream is an LDS read, so f is read from
+// HBM 12 times (Fp2) per product instead of 36 -- 60 Fp2 loads + 12 stores
+// against 78 + 9 with the park holding t0 instead, k_final -1 ms
+// (profiles/round5_w_sweep_apark.txt; k_final's HBM traffic is its clock:
 // the same instruction stream with L2-resident slots runs 2.36 instead of
 // 2.13 GHz, profiles/round5_v_diag_l2.txt).
-#ifndef CESS_FE_APARK
-#define CESS_FE_APARK 1
-#endif
 template <class D, class S, class G, class T, class P>
 CESS_HD void mul12_stream_ap(const D& d, const S& f, const G& g, const T& t, const P& pk) {
 #pragma unroll 1
@@ -450,7 +385,7 @@ CESS_HD void mul12_stream_ap(const D& d, const S& f, const G& g, const T& t, con
   d.st(2, add(t.ld(2), d.ld(4)));
   CESS_MEMBAR();
   // unreduced sums (< 4p) in the park: mul6_stream's own sums of two of them
-  // stay below 8p, mul()'s input bound (as in mul12_stream)
+  // stay below 8p, mul()'s input bound
 #pragma unroll 1
   for (int j = 0; j < 3; j++) pk.st(j, add_nr(f.ld(j), f.ld(3 + j)));
   CESS_MEMBAR();
@@ -549,8 +484,8 @@ CESS_HD void inv12_stream(const D& d, const S& f, const T& t) {
 // ---------------------------------------------------------------------------
 enum FeOp : uint8_t { FE_LOAD, FE_STORE, FE_MUL, FE_SQN, FE_CONJ, FE_FROB, FE_INV, FE_CHAIN, FE_END };
 // SL_X0..SL_X2: FE_CHAIN's powers; SL_XT: the intermediate power of
-// CESS_FE_CYCEXP; SL_TM: FE_MUL's Fp6 temporary when the park caches its first
-// operand (CESS_FE_APARK)
+// CESS_FE_CYCEXP; SL_TM: FE_MUL's Fp6 temporary (the park caches its first
+// operand, mul12_stream_ap)
 enum FeSlot : uint8_t { SL_F = 0, SL_M, SL_T0, SL_T1, SL_T3, SL_T4, SL_T5, SL_T6,
                         SL_X0, SL_X1, SL_X2, SL_XT, SL_TM, SL_N };
 
@@ -698,47 +633,11 @@ CESS_HD void cyc_square_run(const A& acc, const P& pk, int n) {
 // half's two results stay in registers while the (z2, z3) half runs: the run
 // touches no HBM (k_final 171.3 -> 160.8 ms per 1 M against z4, z5 in the HBM
 // accumulator with the results parked in LDS, profiles/r02w_sweep.txt).
-#ifndef CESS_KCYC_LOOP
-#define CESS_KCYC_LOOP 0
-#endif
+// Measured, not adopted: the two halves as a two-pass inner loop over one
+// copy of their products (half the loop body's bytes): k_final 142.7 / 143.4
+// against 142.3 / 143.1 ms (profiles/round5_ay_kfinal_kcyc_loop.txt).
 template <class P>
 CESS_HD void kcyc_run(const P& pk, fp2& z2, fp2& z3, int n) {
-#if CESS_KCYC_LOOP
-  // the two halves share ONE copy of their products (b3 = 3 x y and
-  // t3 = 3 (x + y)(x + xi y)): a two-pass inner loop, (x, y) = (z4, z5) from
-  // the park, then (z2, z3); half the loop body's instruction bytes
-#pragma unroll 1
-  for (int r = 0; r < n; r++) {
-    fp2 u, v;
-#pragma unroll 1
-    for (int h = 0; h < 2; h++) {
-      CESS_MEMBAR();
-      fp2 x, y;
-      if (h) {
-        x = z2;
-        y = z3;
-      } else {
-        x = pk.ld(0);
-        y = pk.ld(1);
-      }
-      const fp2 b3 = mul_scaled<3>(x, y);
-      CESS_MEMBAR();
-      const fp2 t3 = mul_scaled<3>(add_nr(x, y), add_xi_nr(x, y));
-      const fp2 nb3 = mul_nr(b3);
-      const fp2 w = sub(sub(t3, b3), nb3);   // 3 (x^2 + xi y^2)
-      if (h) {
-        pk.st(0, sub(w, dbl(pk.ld(0))));
-        pk.st(1, dbl(add(pk.ld(1), b3)));
-      } else {
-        u = w;
-        v = dbl(nb3);   // 6 xi z4 z5
-      }
-    }
-    CESS_MEMBAR();
-    z2 = add(dbl(z2), v);
-    z3 = sub(u, dbl(z3));
-  }
-#else
 #pragma unroll 1
   for (int r = 0; r < n; r++) {
     CESS_MEMBAR();
@@ -763,7 +662,6 @@ CESS_HD void kcyc_run(const P& pk, fp2& z2, fp2& z3, int n) {
     z2 = add(dbl(z2), v);
     z3 = sub(u, dbl(z3));
   }
-#endif
 }
 
 // numerator / denominator of z1 of a compressed cyclotomic element:
@@ -858,8 +756,8 @@ CESS_HD void cyc_chain(const B& base, XFn&& X, const P& pk, DG* dg = nullptr) {
 
 // Run the program.  The accumulator alternates between the stores acc0 and
 // acc1: FE_MUL writes the product of the current one and a slot into the other
-// (mul12_stream, with the parking store `pk` as its Fp6 temporary); every other
-// opcode works in place.  slot(s) returns the store of slot s (slot SL_F holds
+// (mul12_stream_ap, the parking store `pk` caching its first operand); every
+// other opcode works in place.  slot(s) returns the store of slot s (slot SL_F holds
 // the Miller-loop output on entry); `pk` is also the parking store of
 // cyc_square_run.  Returns the index (0/1) of the store holding the
 // result.
@@ -876,11 +774,7 @@ CESS_HD int final_exp_staged(const A& acc0, const A& acc1, const uint8_t (*prog)
       case FE_LOAD: copy12(acc, slot(arg)); break;
       case FE_STORE: copy12(slot(arg), acc); break;
       case FE_MUL:
-#if CESS_FE_APARK
         mul12_stream_ap(cur ? acc0 : acc1, acc, slot(arg), slot(SL_TM), pk);
-#else
-        mul12_stream(cur ? acc0 : acc1, acc, slot(arg), pk);
-#endif
         cur ^= 1;
         if (dg) dg->template mark<1>();
         break;

@@ -374,14 +374,14 @@ def test_g1_subgroup_check_jacobian(emu):
         assert emu.emu_g1_torsion_free(limbs(x), limbs(y), 1) == want, (x, y)
 
 
-VARIANT_FLAGS = ["-DCESS_SQR12_LOOP=1", "-DCESS_MUL014_LOOP=1", "-DCESS_KCYC_LOOP=1", "-DCESS_MONT_SEP=1", "-DCESS_MUL2=1", "-DCESS_FE_APARK=1"]
+VARIANT_FLAGS = ["-DCESS_MUL014_LOOP=1"]
 
 
 @pytest.fixture(scope="module")
 def emu_loops():
     """The host build of the same headers with the code-size loop forms of the
-    Fp12 operations (sqr12 / mul014 / mul014_one as two-pass loops, the
-    Karabina squaring's halves sharing one copy): staged.hpp CESS_*_LOOP."""
+    sparse Fp12 products (mul014 / mul014_one as two-pass loops, the forms
+    k_miller_rr is built with): staged.hpp CESS_MUL014_LOOP."""
     lib = os.path.join(HERE, "hostemu", "libemu_loops.so")
     hdr_dir = os.path.join(HERE, "..", "cess_amd", "csrc", "bls")
     newest = max(os.path.getmtime(os.path.join(hdr_dir, f)) for f in os.listdir(hdr_dir))

@@ -37,7 +37,7 @@ template <class A> struct MulV6 { A a; __device__ fp2 get(int j) const { return 
 template <class S> struct Sink6 { const S& s; int h; __device__ void put(int j, const fp2& x) const { s.st(3 * h + j, x); } };
 
 template <class VA, class VB, class O>
-__device__ __forceinline__ void mul6_stream(const VA& A, const VB& B, const O& out) {
+__device__ __forceinline__ void mul6_view(const VA& A, const VB& B, const O& out) {
   fp2 v0 = mul(A.get(0), B.get(0));
   CESS_MEMBAR();
   fp2 v1 = mul(A.get(1), B.get(1));
@@ -54,8 +54,8 @@ __device__ __forceinline__ void mul6_stream(const VA& A, const VB& B, const O& o
 template <class S, class T>
 __device__ __forceinline__ void sqr12_stream(const S& f, const T& t) {
   Half6<S> a0{f, 0}, a1{f, 1};
-  mul6_stream(a0, a1, Sink6<T>{t, 0});                                   // ab
-  mul6_stream(Sum6<Half6<S>, Half6<S>>{a0, a1}, Sum6<Half6<S>, MulV6<Half6<S>>>{a0, {a1}}, Sink6<T>{t, 1});  // X
+  mul6_view(a0, a1, Sink6<T>{t, 0});                                   // ab
+  mul6_view(Sum6<Half6<S>, Half6<S>>{a0, a1}, Sum6<Half6<S>, MulV6<Half6<S>>>{a0, {a1}}, Sink6<T>{t, 1});  // X
 #pragma unroll 1
   for (int j = 0; j < 3; j++) {
     fp2 ab = t.ld(j), vab = j == 0 ? mul_nr(t.ld(2)) : t.ld(j - 1);

@@ -136,12 +136,11 @@ __global__ __launch_bounds__(256) void k_fp(uint64_t* out, const uint32_t* in, i
     if (OP == 0) a = mul(a, b);                   // lazy Fp2 product
     if (OP == 1) a = sub(add(a, b), dbl(b));      // Fp2 add/sub chains
     if (OP == 2) a = dot2(a, b, b, a);            // one-reduction a b + c d
-    if (OP == 3) mul2(a, b, b, a, a, b);          // two independent products, one column loop
-    if (OP == 4) a = mul_sep<1>(a, b);            // column sums off the reduction chain
-    if (OP == 5) a = mul_sep<2>(a, b);            // ... split by digit parity
-    if (OP == 6) a = mul_sep<2, false>(a, b);     // ... m*p terms on the second a*b chain
-    if (OP == 7) a = mul_sep<2, false, true>(a, b);
-    if (OP == 8) a = mul_sep<3, false>(a, b);
+    if (OP == 3) a = mul_sep<1>(a, b);            // column sums off the reduction chain
+    if (OP == 4) a = mul_sep<2>(a, b);            // ... split by digit parity
+    if (OP == 5) a = mul_sep<2, false>(a, b);     // ... m*p terms on the second a*b chain
+    if (OP == 6) a = mul_sep<2, false, true>(a, b);
+    if (OP == 7) a = mul_sep<3, false>(a, b);
   }
   __builtin_amdgcn_sched_barrier(0);
   const uint64_t t1 = stamp();
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(256) void k_fp(uint64_t* out, const uint32_t* in, i
   const int w = blockIdx.x * 4 + threadIdx.x / 64;
   if ((threadIdx.x & 63) == 0) out[2 * w] = t1 - t0;
   if (r == 0x12345678u) out[2 * w + 1] = r;
-  if (OP >= 4 && iters == 1) {   // one step: compare with the shipped product
+  if (OP >= 3 && iters == 1) {   // one step: compare with the shipped product
     fp2 a1, b1;
 #pragma unroll
     for (int i = 0; i < 12; i++) {
@@ -172,10 +171,10 @@ int main() {
   hipDeviceProp_t prop;
   CHK(hipGetDeviceProperties(&prop, 0));
   const int cus = prop.multiProcessorCount, iters = 2048;
-  const char* names[9] = {"mul(fp2,fp2)", "sub(add,dbl) fp2", "dot2", "mul2 (2 products)", "mul_sep<1>", "mul_sep<2>",
+  const char* names[8] = {"mul(fp2,fp2)", "sub(add,dbl) fp2", "dot2", "mul_sep<1>", "mul_sep<2>",
                           "mul_sep<2,noq>", "mul_sep<2,bal>", "mul_sep<3,noq>"};
-  void (*fns[9])(uint64_t*, const uint32_t*, int) = {k_fp<0>, k_fp<1>, k_fp<2>, k_fp<3>, k_fp<4>, k_fp<5>,
-                                                      k_fp<6>, k_fp<7>, k_fp<8>};
+  void (*fns[8])(uint64_t*, const uint32_t*, int) = {k_fp<0>, k_fp<1>, k_fp<2>, k_fp<3>, k_fp<4>, k_fp<5>,
+                                                      k_fp<6>, k_fp<7>};
   uint64_t* out;
   uint32_t* in;
   CHK(hipMalloc(&out, (size_t)cus * 8 * 4 * 16));
@@ -188,8 +187,8 @@ int main() {
   for (auto f : fns) CHK(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
   printf("# cycles per loop iteration per wave (in-kernel s_memtime, median over waves)\n");
   printf("%-18s %10s %10s\n", "op", "W=1", "W=2");
-  for (int v = 0; v < 9; v++) {
-    if (v >= 4) {   // correctness of the separated forms: one step against mul()
+  for (int v = 0; v < 8; v++) {
+    if (v >= 3) {   // correctness of the separated forms: one step against mul()
       hipLaunchKernelGGL(fns[v], dim3(cus), dim3(256), 0, 0, out, in, 1);
       CHK(hipDeviceSynchronize());
       CHK(hipMemcpy(h.data(), out, (size_t)cus * 4 * 16, hipMemcpyDeviceToHost));
