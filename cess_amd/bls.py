@@ -58,12 +58,18 @@ EXPORTS = (
     # hashed mode (RSASSA-PKCS1-v1_5 with SHA-256, on-GPU hashing) and the key policies
     "cess_rsa_parse_key_policy", "cess_rsa_keys_load_policy", "cess_rsa_verify_sha256_batch",
     "cess_rsa_verify_sha256_batch_device", "cess_rsa_verify_sha256",
+    # SHA-384 / SHA-512 and the four algorithms of SUPPORTED_SIG_ALGS
+    "cess_rsa_verify_digest_batch", "cess_rsa_verify_digest_batch_device", "cess_rsa_verify_alg",
 )
 # exported too, outside the cess_bls_ / cess_rsa_ name space that EXPORTS lists
-EXPORTS_OTHER = ("cess_sha256_batch",)
+EXPORTS_OTHER = ("cess_sha256_batch", "cess_sha2_batch")
 RSA_E_UNSUPPORTED = -10
 RSA_KEY_SPKI, RSA_KEY_PKCS1 = 0, 1
-RSA_POLICY_RSA_CRATE, RSA_POLICY_RING_2048_8192 = 0, 1   # include/cess_rsa.h CESS_RSA_POLICY_*
+RSA_POLICY_RSA_CRATE, RSA_POLICY_RING_2048_8192, RSA_POLICY_RING_3072_8192 = 0, 1, 2   # CESS_RSA_POLICY_*
+RSA_DIGEST_SHA256, RSA_DIGEST_SHA384, RSA_DIGEST_SHA512 = 0, 1, 2                      # CESS_RSA_DIGEST_*
+RSA_DIGEST_BYTES = {RSA_DIGEST_SHA256: 32, RSA_DIGEST_SHA384: 48, RSA_DIGEST_SHA512: 64}
+# the four entries of SUPPORTED_SIG_ALGS (CESS_RSA_ALG_*): digest + key policy
+RSA_ALG_2048_8192_SHA256, RSA_ALG_2048_8192_SHA384, RSA_ALG_2048_8192_SHA512, RSA_ALG_3072_8192_SHA384 = 0, 1, 2, 3
 RSA_CODE_NAMES = {0: "OK", 1: "SIG_LEN", 2: "SIG_RANGE", 3: "MSG_LEN", 4: "MISMATCH", 5: "KEY"}
 
 # infrastructure status codes (include/cess_bls.h)
@@ -180,6 +186,12 @@ def load_library(path: str = LIB_PATH):
             lib.cess_rsa_verify_sha256.argtypes = [vp, _u8p, sz, ctypes.c_int, _u8p, sz, _u8p, sz,
                                                    ctypes.POINTER(ctypes.c_int)]
             lib.cess_sha256_batch.argtypes = [vp, sz, _u8p, _u64p, _u8p]
+        if hasattr(lib, "cess_rsa_verify_digest_batch"):   # (likewise)
+            lib.cess_rsa_verify_digest_batch.argtypes = [vp, ctypes.c_int] + lib.cess_rsa_verify_batch.argtypes[1:]
+            lib.cess_rsa_verify_digest_batch_device.argtypes = [vp, ctypes.c_int, sz, vp, vp, vp, vp, vp, vp, vp]
+            lib.cess_rsa_verify_alg.argtypes = [vp, ctypes.c_int, _u8p, sz, ctypes.c_int, _u8p, sz, _u8p, sz,
+                                                ctypes.POINTER(ctypes.c_int)]
+            lib.cess_sha2_batch.argtypes = [vp, ctypes.c_int, sz, _u8p, _u64p, _u8p]
         lib.cess_bls_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
                                              _u64p, ctypes.c_int, ctypes.c_int]
         lib.cess_bls_launch_records.argtypes = [vp]
@@ -620,6 +632,46 @@ class Context:
         self._chk(self._lib.cess_sha256_batch(self._h, n, _buf(b"".join(msgs)), _offsets([len(m) for m in msgs]), out))
         raw = bytes(out)
         return [raw[32 * i:32 * (i + 1)] for i in range(n)]
+
+    # --- the same with SHA-384 / SHA-512: the four algorithms of SUPPORTED_SIG_ALGS ---
+    def rsa_verify_digest_batch(self, digest: int, key_idx: Sequence[int], msgs: Sequence[bytes],
+                                sigs: Sequence[bytes], with_bitmap: bool = False):
+        """rsa_verify_sha256_batch with the digest chosen by RSA_DIGEST_*."""
+        n = len(key_idx)
+        idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        bitmap = (ctypes.c_uint64 * max((n + 63) // 64, 1))()
+        self._chk(self._lib.cess_rsa_verify_digest_batch(self._h, digest, n, idx, _buf(b"".join(sigs)),
+                                                         _offsets([len(x) for x in sigs]), _buf(b"".join(msgs)),
+                                                         _offsets([len(m) for m in msgs]), codes, bitmap))
+        if with_bitmap:
+            return bytes(codes)[:n], list(bitmap)[: (n + 63) // 64]
+        return bytes(codes)[:n]
+
+    def rsa_verify_digest_batch_device(self, digest, n, d_key_idx, d_sigs, d_sig_offs, d_msgs, d_msg_offs, d_codes,
+                                       stream=0):
+        self._chk(self._lib.cess_rsa_verify_digest_batch_device(self._h, digest, n, d_key_idx, d_sigs, d_sig_offs,
+                                                                d_msgs, d_msg_offs, d_codes, stream or None))
+
+    def verify_rsa_alg(self, alg: int, key_der: bytes, msg: bytes, sig: bytes, fmt: int = RSA_KEY_SPKI) -> bool:
+        """verify_signature(alg, msg, sig) for one of the four RSA_ALG_* (enclave-verify/src/lib.rs:87-93)
+        under that algorithm's key policy; raises BlsInfraError(E_BAD_KEY / RSA_E_UNSUPPORTED) for the key."""
+        ok = ctypes.c_int()
+        key_der, msg, sig = bytes(key_der), bytes(msg), bytes(sig)
+        self._chk(self._lib.cess_rsa_verify_alg(self._h, alg, _buf(key_der), len(key_der), fmt, _buf(msg), len(msg),
+                                                _buf(sig), len(sig), ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def sha2_batch(self, digest: int, msgs: Sequence[bytes]) -> list:
+        """SHA-256 / SHA-384 / SHA-512 (RSA_DIGEST_*) of every message: the digest kernels alone."""
+        if digest not in RSA_DIGEST_BYTES:
+            raise BlsInfraError("unknown digest", E_INVALID_ARG)
+        n, w = len(msgs), RSA_DIGEST_BYTES[digest]
+        out = (ctypes.c_uint8 * (w * max(n, 1)))()
+        self._chk(self._lib.cess_sha2_batch(self._h, digest, n, _buf(b"".join(msgs)),
+                                            _offsets([len(m) for m in msgs]), out))
+        raw = bytes(out)
+        return [raw[w * i:w * (i + 1)] for i in range(n)]
 
     # --- generator side -------------------------------------------------
     def public_keys_raw(self, sks: bytes) -> bytes:

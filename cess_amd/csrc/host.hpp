@@ -358,8 +358,9 @@ int cess_gen_one(cess_bls_ctx* c, int kind, size_t n, const uint8_t* sks, const 
                  uint8_t* out);
 int cess_rsa_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                  const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
-int cess_rsa_sha256_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
-                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_rsa_digest_one(cess_bls_ctx* s, int digest, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                        const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                        uint64_t* bitmap_out);
 void cess_rsa_state_free(cess_bls_ctx* c);
 // one process, several GPUs (host_multi.cpp)
 int cess_multi_create(const cess_bls_config* cfg, int ndev, cess_bls_ctx* c);
@@ -378,6 +379,6 @@ int cess_multi_gt(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t*
                   const uint64_t* offs, uint8_t* codes_out, uint8_t* gt_out);
 int cess_multi_rsa(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                    const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
-int cess_multi_rsa_sha256(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+int cess_multi_rsa_digest(cess_bls_ctx* c, int digest, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
                           const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
                           uint64_t* bitmap_out);

@@ -31,6 +31,8 @@ __global__ void k_rsa_scatter(uint64_t, const uint32_t*, uint32_t, const RsaKeyD
                               const uint64_t*, const uint32_t*, uint32_t*, uint32_t*, uint64_t);
 // hashed mode front end (k_rsa_digest.hip): T_i = DigestInfo || SHA-256(msg_i), or the digests alone
 __global__ void k_rsa_digest(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*);
+// its SHA-384 / SHA-512 sibling (k_rsa_digest512.hip); the last argument is CESS_RSA_DIGEST_SHA384 or _SHA512
+__global__ void k_rsa_digest512(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*, int);
 // key-uniform lists when the table has at most this many keys and the batch at
 // least this many records per key (padding each (class, key) segment to a
 // multiple of 64 then costs < 25 % idle lanes in the worst case)
@@ -89,16 +91,19 @@ bool parse_pkcs1(const uint8_t* b, size_t n, std::vector<uint8_t>& mod, uint64_t
   if (eb.size() > 8) return false;
   e = 0;
   for (uint8_t v : eb) e = (e << 8) | v;
-  if (policy == CESS_RSA_POLICY_RING_2048_8192) {
-    // ring's Key::from_modulus_and_exponent under RSA_PKCS1_2048_8192_SHA256
+  if (policy == CESS_RSA_POLICY_RING_2048_8192 || policy == CESS_RSA_POLICY_RING_3072_8192) {
+    // ring's Key::from_modulus_and_exponent under RSA_PKCS1_2048_8192_SHA256 /
+    // _SHA384 / _SHA512 and RSA_PKCS1_3072_8192_SHA384
     // (src/rsa/verification.rs:30-80, arithmetic/bigint.rs:251-263, 683-728):
-    // the modulus length rounded up to whole bytes is at least 2048 bits (so
-    // 2041..2047-bit moduli pass, as in ring) and the exact length at most
-    // 8192; n odd; e odd with 3 <= e <= 2^33 - 1
+    // the modulus length rounded up to whole bytes is at least the floor of
+    // 2048 or 3072 bits (so 2041..2047- and 3065..3071-bit moduli pass, as in
+    // ring) and the exact length at most 8192; n odd; e odd with
+    // 3 <= e <= 2^33 - 1
     if (mod.empty()) return false;
     size_t bits = 8 * mod.size();
     for (uint8_t v = mod[0]; !(v & 0x80); v <<= 1) bits--;
-    if (8 * mod.size() < 2048 || bits > 8192) return false;
+    const size_t floor_bits = policy == CESS_RSA_POLICY_RING_3072_8192 ? 3072 : 2048;
+    if (8 * mod.size() < floor_bits || bits > 8192) return false;
     if (!(mod.back() & 1)) return false;
     return (e & 1) && e >= 3 && e <= (1ull << 33) - 1;
   }
@@ -220,7 +225,7 @@ struct RsaTable {
 struct RsaState {
   RsaTable user, single;
   DevBuf lists, counts, base, in_idx, in_sigs, in_soffs, in_msgs, in_moffs, out_codes;
-  DevBuf t, t_offs;   // hashed mode: T_i at stride 51 and its offsets (k_rsa_digest)
+  DevBuf t, t_offs;   // hashed mode: T_i at stride 51 / 67 / 83 and its offsets (k_rsa_digest, k_rsa_digest512)
 };
 
 static RsaState& rsa_state(cess_bls_ctx* c) {
@@ -348,40 +353,55 @@ static int rsa_run(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, cons
   return CESS_BLS_OK;
 }
 
-// k_rsa_digest over device-resident messages, enqueued on s: `out` receives
-// 64 (n / 64 + 1) records of 51 (prefix) or 32 bytes, t_offs (prefix only)
-// n + 1 offsets
+// bytes of one digest (CESS_RSA_DIGEST_*), 0 for an unknown selector; T_i is
+// the 19-byte DigestInfo prefix and the digest
+static size_t digest_bytes(int digest) {
+  return digest == CESS_RSA_DIGEST_SHA256 ? 32 : digest == CESS_RSA_DIGEST_SHA384 ? 48
+         : digest == CESS_RSA_DIGEST_SHA512 ? 64 : 0;
+}
+static size_t t_bytes(int digest) { return 19 + digest_bytes(digest); }
+
+// the digest kernel over device-resident messages, enqueued on s: `out`
+// receives 64 (n / 64 + 1) records of t_bytes (prefix) or digest_bytes,
+// t_offs (prefix only) n + 1 offsets.  Both kernels are the ST_RSA_DIGEST stage.
 static size_t digest_records(uint64_t n) { return 64 * (n / 64 + 1); }
-static int digest_run(cess_bls_ctx* c, hipStream_t s, uint64_t n, const uint8_t* d_msgs, const uint64_t* d_moffs,
-                      uint8_t* out, bool prefix, uint64_t* t_offs) {
+static int digest_run(cess_bls_ctx* c, hipStream_t s, int digest, uint64_t n, const uint8_t* d_msgs,
+                      const uint64_t* d_moffs, uint8_t* out, bool prefix, uint64_t* t_offs) {
   hipEvent_t a;
   int r = prof_begin(c, s, ST_RSA_DIGEST, &a);
   if (r) return r;
-  hipLaunchKernelGGL(k_rsa_digest, dim3((unsigned)(n / 64 + 1)), dim3(64), 0, s, n, d_msgs, d_moffs, out,
-                     prefix ? 1u : 0u, t_offs);
+  if (digest == CESS_RSA_DIGEST_SHA256)
+    hipLaunchKernelGGL(k_rsa_digest, dim3((unsigned)(n / 64 + 1)), dim3(64), 0, s, n, d_msgs, d_moffs, out,
+                       prefix ? 1u : 0u, t_offs);
+  else
+    hipLaunchKernelGGL(k_rsa_digest512, dim3((unsigned)(n / 64 + 1)), dim3(64), 0, s, n, d_msgs, d_moffs, out,
+                       prefix ? 1u : 0u, t_offs, digest);
   r = prof_end(c, s, ST_RSA_DIGEST, a);
   if (r) return r;
   HIPCHK(hipGetLastError());
   return CESS_BLS_OK;
 }
 
-// hashed mode: T_i = DigestInfo || SHA-256(msg_i) into the context's buffer,
-// then the raw path over (T, t_offs) in place of (msgs, msg_offs)
-static int rsa_run_sha256(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, const uint32_t* d_idx,
+// hashed mode: T_i = DigestInfo || H(msg_i) (H = `digest`, a known selector)
+// into the context's buffer, then the raw path over (T, t_offs) in place of
+// (msgs, msg_offs)
+static int rsa_run_sha256(cess_bls_ctx* c, RsaTable& T, hipStream_t s, int digest, uint64_t n, const uint32_t* d_idx,
                           const uint8_t* d_sigs, const uint64_t* d_soffs, const uint8_t* d_msgs,
                           const uint64_t* d_moffs, uint8_t* d_codes) {
   if (n == 0) return CESS_BLS_OK;
   if (n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
   RsaState& S = rsa_state(c);
-  if (S.t.ensure(digest_records(n) * 51) | S.t_offs.ensure((n + 1) * 8)) return CESS_BLS_E_OOM;
-  int r = digest_run(c, s, n, d_msgs, d_moffs, S.t.as<uint8_t>(), true, S.t_offs.as<uint64_t>());
+  if (S.t.ensure(digest_records(n) * t_bytes(digest)) | S.t_offs.ensure((n + 1) * 8)) return CESS_BLS_E_OOM;
+  int r = digest_run(c, s, digest, n, d_msgs, d_moffs, S.t.as<uint8_t>(), true, S.t_offs.as<uint64_t>());
   if (r) return r;
   return rsa_run(c, T, s, n, d_idx, d_sigs, d_soffs, S.t.as<uint8_t>(), S.t_offs.as<uint64_t>(), d_codes);
 }
 
+// digest: a CESS_RSA_DIGEST_* selector for the hashed mode, kRawMode for the raw one
+constexpr int kRawMode = -1;
 static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
                     const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
-                    uint64_t* bitmap_out, bool sha256 = false) {
+                    uint64_t* bitmap_out, int digest = kRawMode) {
   if (n == 0) return CESS_BLS_OK;
   if (!key_idx || !soffs || !moffs) return CESS_BLS_E_INVALID_ARG;
   RsaState& S = rsa_state(c);
@@ -398,13 +418,17 @@ static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_
     return CESS_BLS_E_INVALID_ARG;
   if (S.in_idx.ensure(n * 4) | S.out_codes.ensure(n)) return CESS_BLS_E_OOM;
   r = upload_msgs(s, sigs, s0, sb, so, S.in_sigs, S.in_soffs);
-  // k_rsa_digest fetches whole dwords (rsa_digest.hpp): 4 bytes of slack
+  // the digest kernels fetch whole dwords (rsa_digest.hpp): 4 bytes of slack
   if (!r) r = upload_msgs(s, msgs, m0, mb, mo, S.in_msgs, S.in_moffs, 4);
   if (r) return r;
   HIPCHK(hipMemcpyAsync(S.in_idx.p, key_idx, n * 4, hipMemcpyHostToDevice, s));
-  r = (sha256 ? rsa_run_sha256 : rsa_run)(c, T, s, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(),
-                                          S.in_soffs.as<uint64_t>(), S.in_msgs.as<uint8_t>(),
-                                          S.in_moffs.as<uint64_t>(), S.out_codes.as<uint8_t>());
+  if (digest == kRawMode)
+    r = rsa_run(c, T, s, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(), S.in_soffs.as<uint64_t>(),
+                S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.out_codes.as<uint8_t>());
+  else
+    r = rsa_run_sha256(c, T, s, digest, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(),
+                       S.in_soffs.as<uint64_t>(), S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(),
+                       S.out_codes.as<uint8_t>());
   if (r) return r;
   std::vector<uint8_t> codes(n);
   HIPCHK(hipMemcpyAsync(codes.data(), S.out_codes.p, n, hipMemcpyDeviceToHost, s));
@@ -432,7 +456,8 @@ extern "C" int cess_rsa_parse_key(const uint8_t* der, size_t len, int format, ui
 }
 
 static bool policy_known(int policy) {
-  return policy == CESS_RSA_POLICY_RSA_CRATE || policy == CESS_RSA_POLICY_RING_2048_8192;
+  return policy == CESS_RSA_POLICY_RSA_CRATE || policy == CESS_RSA_POLICY_RING_2048_8192 ||
+         policy == CESS_RSA_POLICY_RING_3072_8192;
 }
 
 extern "C" int cess_rsa_parse_key_policy(const uint8_t* der, size_t len, int format, int policy, uint8_t* n_out,
@@ -503,42 +528,76 @@ extern "C" int cess_rsa_verify_batch_device(cess_bls_ctx* c, size_t n, const uin
   return call_end(c, s);
 }
 
-// --- hashed mode: RSASSA-PKCS1-v1_5 with SHA-256 -----------------------------
-int cess_rsa_sha256_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
-                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out) {
-  return rsa_host(s, rsa_state(s).user, n, key_idx, sigs, soffs, msgs, moffs, codes_out, bitmap_out, true);
+// --- hashed mode: RSASSA-PKCS1-v1_5 with SHA-256 / SHA-384 / SHA-512 ----------
+int cess_rsa_digest_one(cess_bls_ctx* s, int digest, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                        const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                        uint64_t* bitmap_out) {
+  return rsa_host(s, rsa_state(s).user, n, key_idx, sigs, soffs, msgs, moffs, codes_out, bitmap_out, digest);
+}
+
+extern "C" int cess_rsa_verify_digest_batch(cess_bls_ctx* c, int digest, size_t n, const uint32_t* key_idx,
+                                            const uint8_t* sigs, const uint64_t* sig_offsets, const uint8_t* msgs,
+                                            const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out) {
+  ENTRY(c);
+  if (!digest_bytes(digest)) return CESS_BLS_E_INVALID_ARG;
+  if (!c->subs.empty())
+    return cess_multi_rsa_digest(c, digest, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out);
+  return rsa_host(c, rsa_state(c).user, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out,
+                  digest);
+}
+
+extern "C" int cess_rsa_verify_digest_batch_device(cess_bls_ctx* c, int digest, size_t n, const uint32_t* d_key_idx,
+                                                   const uint8_t* d_sigs, const uint64_t* d_sig_offsets,
+                                                   const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
+                                                   uint8_t* d_codes, void* stream) {
+  ENTRY(c);
+  if (!digest_bytes(digest) || !c->subs.empty() ||
+      (n && (!d_key_idx || !d_sig_offsets || !d_msg_offsets || !d_codes)))
+    return CESS_BLS_E_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  int r = order_begin(c, s);
+  if (r) return r;
+  r = rsa_run_sha256(c, rsa_state(c).user, s, digest, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs, d_msg_offsets,
+                     d_codes);
+  if (r) return r;
+  return call_end(c, s);
 }
 
 extern "C" int cess_rsa_verify_sha256_batch(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
                                             const uint64_t* sig_offsets, const uint8_t* msgs,
                                             const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out) {
-  ENTRY(c);
-  if (!c->subs.empty())
-    return cess_multi_rsa_sha256(c, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out);
-  return rsa_host(c, rsa_state(c).user, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out,
-                  true);
+  return cess_rsa_verify_digest_batch(c, CESS_RSA_DIGEST_SHA256, n, key_idx, sigs, sig_offsets, msgs, msg_offsets,
+                                      codes_out, bitmap_out);
 }
 
 extern "C" int cess_rsa_verify_sha256_batch_device(cess_bls_ctx* c, size_t n, const uint32_t* d_key_idx,
                                                    const uint8_t* d_sigs, const uint64_t* d_sig_offsets,
                                                    const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
                                                    uint8_t* d_codes, void* stream) {
-  ENTRY(c);
-  if (!c->subs.empty() || (n && (!d_key_idx || !d_sig_offsets || !d_msg_offsets || !d_codes)))
-    return CESS_BLS_E_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  int r = order_begin(c, s);
-  if (r) return r;
-  r = rsa_run_sha256(c, rsa_state(c).user, s, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs, d_msg_offsets, d_codes);
-  if (r) return r;
-  return call_end(c, s);
+  return cess_rsa_verify_digest_batch_device(c, CESS_RSA_DIGEST_SHA256, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs,
+                                             d_msg_offsets, d_codes, stream);
 }
 
-extern "C" int cess_rsa_verify_sha256(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, int format,
-                                      const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len,
-                                      int* ok_out) {
+// the four entries of SUPPORTED_SIG_ALGS (enclave-verify/src/lib.rs:87-93): digest and key policy
+static bool alg_of(int alg, int* digest, int* policy) {
+  static const int kAlgs[4][2] = {
+      {CESS_RSA_DIGEST_SHA256, CESS_RSA_POLICY_RING_2048_8192},   // CESS_RSA_ALG_2048_8192_SHA256
+      {CESS_RSA_DIGEST_SHA384, CESS_RSA_POLICY_RING_2048_8192},   // CESS_RSA_ALG_2048_8192_SHA384
+      {CESS_RSA_DIGEST_SHA512, CESS_RSA_POLICY_RING_2048_8192},   // CESS_RSA_ALG_2048_8192_SHA512
+      {CESS_RSA_DIGEST_SHA384, CESS_RSA_POLICY_RING_3072_8192}};  // CESS_RSA_ALG_3072_8192_SHA384
+  if (alg < 0 || alg > CESS_RSA_ALG_3072_8192_SHA384) return false;
+  *digest = kAlgs[alg][0];
+  *policy = kAlgs[alg][1];
+  return true;
+}
+
+extern "C" int cess_rsa_verify_alg(cess_bls_ctx* c, int alg, const uint8_t* key_der, size_t key_len, int format,
+                                   const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len,
+                                   int* ok_out) {
   ENTRY(c);
+  int digest = 0, policy = 0;
+  if (!alg_of(alg, &digest, &policy)) return CESS_BLS_E_INVALID_ARG;
   if (!ok_out || (!key_der && key_len) || (!msg && msg_len) || (!sig && sig_len)) return CESS_BLS_E_INVALID_ARG;
   if (format != CESS_RSA_KEY_SPKI && format != CESS_RSA_KEY_PKCS1) return CESS_BLS_E_INVALID_ARG;
   *ok_out = 0;
@@ -547,23 +606,32 @@ extern "C" int cess_rsa_verify_sha256(cess_bls_ctx* c, const uint8_t* key_der, s
   const uint64_t ko[2] = {0, key_len};
   int st = CESS_BLS_OK;
   RsaTable& T = rsa_state(d).single;
-  int r = load_table(d, T, 1, key_der ? key_der : &zero, ko, format, &st, CESS_RSA_POLICY_RING_2048_8192);
+  int r = load_table(d, T, 1, key_der ? key_der : &zero, ko, format, &st, policy);
   if (r) return r;
   if (st) return st;   // ring rejects the key (BAD_KEY) or the GPU cannot verify it (UNSUPPORTED)
   const uint32_t idx = 0;
   const uint64_t so[2] = {0, sig_len}, mo[2] = {0, msg_len};
   uint8_t code = 0xff;
-  r = rsa_host(d, T, 1, &idx, sig ? sig : &zero, so, msg ? msg : &zero, mo, &code, nullptr, true);
+  r = rsa_host(d, T, 1, &idx, sig ? sig : &zero, so, msg ? msg : &zero, mo, &code, nullptr, digest);
   if (r) return r;
   *ok_out = code == RSA_OK;
   return CESS_BLS_OK;
 }
 
-extern "C" int cess_sha256_batch(cess_bls_ctx* c, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets,
-                                 uint8_t* out32) {
+extern "C" int cess_rsa_verify_sha256(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, int format,
+                                      const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len,
+                                      int* ok_out) {
+  return cess_rsa_verify_alg(c, CESS_RSA_ALG_2048_8192_SHA256, key_der, key_len, format, msg, msg_len, sig, sig_len,
+                             ok_out);
+}
+
+extern "C" int cess_sha2_batch(cess_bls_ctx* c, int digest, size_t n, const uint8_t* msgs,
+                               const uint64_t* msg_offsets, uint8_t* out) {
   ENTRY(c);
+  const size_t db = digest_bytes(digest);
+  if (!db) return CESS_BLS_E_INVALID_ARG;
   if (n == 0) return CESS_BLS_OK;
-  if (!msg_offsets || !out32 || n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
+  if (!msg_offsets || !out || n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
   cess_bls_ctx* d = c->subs.empty() ? c : c->subs[0];
   RsaState& S = rsa_state(d);
   HIPCHK(hipSetDevice(d->device));
@@ -573,14 +641,20 @@ extern "C" int cess_sha256_batch(cess_bls_ctx* c, size_t n, const uint8_t* msgs,
   std::vector<uint64_t> mo;
   uint64_t m0, mb;
   if (!rebase_offsets(msg_offsets, 0, n, msgs != nullptr, mo, &m0, &mb)) return CESS_BLS_E_INVALID_ARG;
-  if (S.t.ensure(digest_records(n) * 32)) return CESS_BLS_E_OOM;
+  if (S.t.ensure(digest_records(n) * db)) return CESS_BLS_E_OOM;
   r = upload_msgs(s, msgs, m0, mb, mo, S.in_msgs, S.in_moffs, 4);
   if (r) return r;
-  r = digest_run(d, s, n, S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.t.as<uint8_t>(), false, nullptr);
+  r = digest_run(d, s, digest, n, S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.t.as<uint8_t>(), false,
+                 nullptr);
   if (r) return r;
-  HIPCHK(hipMemcpyAsync(out32, S.t.p, n * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(out, S.t.p, n * db, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return call_end(d, s);
+}
+
+extern "C" int cess_sha256_batch(cess_bls_ctx* c, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                 uint8_t* out32) {
+  return cess_sha2_batch(c, CESS_RSA_DIGEST_SHA256, n, msgs, msg_offsets, out32);
 }
 
 extern "C" int cess_rsa_verify(cess_bls_ctx* c, const uint8_t* key_der, size_t key_len, const uint8_t* msg,

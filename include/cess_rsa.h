@@ -149,6 +149,62 @@ int cess_rsa_verify_sha256(cess_bls_ctx* ctx, const uint8_t* key_der, size_t key
  * mode's digest kernel alone, exposed for tests. */
 int cess_sha256_batch(cess_bls_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets, uint8_t* out32);
 
+/* ---------------------------------------------------------------------------
+ * The other digests of verify_miner_cert's SUPPORTED_SIG_ALGS (reference
+ * primitives/enclave-verify/src/lib.rs:87-93): RSASSA-PKCS1-v1_5 with SHA-384
+ * and SHA-512, hashed on the GPU (k_rsa_digest512), and ring's 3072-bit key
+ * floor.  T_i = DigestInfo(H) || H(msg_i) is 51 / 67 / 83 bytes for SHA-256 /
+ * SHA-384 / SHA-512; everything after the hashing is the raw path, as above.
+ *
+ *   CESS_RSA_POLICY_RING_3072_8192  ring's key checks under
+ *     RSA_PKCS1_3072_8192_SHA384: CESS_RSA_POLICY_RING_2048_8192 with a floor
+ *     of 3072 bits, compared as ring does against the modulus length rounded
+ *     up to whole bytes (a 3065-bit modulus passes, a 3064-bit one does not).
+ *     Keys longer than 4096 bits that pass are CESS_RSA_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+#define CESS_RSA_DIGEST_SHA256 0
+#define CESS_RSA_DIGEST_SHA384 1
+#define CESS_RSA_DIGEST_SHA512 2
+#define CESS_RSA_POLICY_RING_3072_8192 2
+/* the four entries of SUPPORTED_SIG_ALGS: digest + key policy */
+#define CESS_RSA_ALG_2048_8192_SHA256 0
+#define CESS_RSA_ALG_2048_8192_SHA384 1
+#define CESS_RSA_ALG_2048_8192_SHA512 2
+#define CESS_RSA_ALG_3072_8192_SHA384 3
+
+/* cess_rsa_verify_sha256_batch with the digest chosen by `digest`
+ * (CESS_RSA_DIGEST_*; an unknown value is CESS_BLS_E_INVALID_ARG; SHA256 is
+ * cess_rsa_verify_sha256_batch itself).  CESS_RSA_MSG_LEN means
+ * k < len(T) + 11: k < 62, 78 or 94.  Runs over whatever table is loaded. */
+int cess_rsa_verify_digest_batch(cess_bls_ctx* ctx, int digest, size_t n, const uint32_t* key_idx,
+                                 const uint8_t* sigs, const uint64_t* sig_offsets, const uint8_t* msgs,
+                                 const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out);
+
+/* Device-resident form: pointers, stream, the ordering of d_msg_offsets and
+ * the read bounds exactly as cess_rsa_verify_sha256_batch_device: message
+ * bytes are fetched as whole aligned dwords, and only dwords that hold a
+ * message byte, so the kernel may read up to 3 bytes before d_msgs (if d_msgs
+ * is not 4-byte aligned) and up to 3 bytes past d_msgs + d_msg_offsets[n],
+ * never beyond the aligned dword of the first / last byte. */
+int cess_rsa_verify_digest_batch_device(cess_bls_ctx* ctx, int digest, size_t n, const uint32_t* d_key_idx,
+                                        const uint8_t* d_sigs, const uint64_t* d_sig_offsets, const uint8_t* d_msgs,
+                                        const uint64_t* d_msg_offsets, uint8_t* d_codes, void* stream);
+
+/* verify_signature(alg, msg, sig) drop-in for one record and one of the four
+ * algorithms (CESS_RSA_ALG_*; an unknown value is CESS_BLS_E_INVALID_ARG;
+ * alg 0 is cess_rsa_verify_sha256): the key, in `format`, is loaded under the
+ * algorithm's key policy.  CESS_BLS_E_BAD_KEY where ring rejects the key,
+ * CESS_RSA_E_UNSUPPORTED where the GPU cannot verify it; else *ok_out = the
+ * verdict. */
+int cess_rsa_verify_alg(cess_bls_ctx* ctx, int alg, const uint8_t* key_der, size_t key_len, int format,
+                        const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len, int* ok_out);
+
+/* H(msg_i) of n messages (host buffers) -> out (32 / 48 / 64 bytes per
+ * record): the digest kernels alone, exposed for tests.  digest = SHA256 is
+ * cess_sha256_batch. */
+int cess_sha2_batch(cess_bls_ctx* ctx, int digest, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets,
+                    uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

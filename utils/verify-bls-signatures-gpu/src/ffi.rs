@@ -208,10 +208,32 @@ extern "C" {
                                   ok_out: *mut c_int) -> c_int;
     pub fn cess_sha256_batch(ctx: *mut cess_bls_ctx, n: usize, msgs: *const u8, msg_offsets: *const u64,
                              out32: *mut u8) -> c_int;
+
+    // SHA-384 / SHA-512 and the four algorithms of SUPPORTED_SIG_ALGS (enclave-verify/src/lib.rs:87-93)
+    pub fn cess_rsa_verify_digest_batch(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, key_idx: *const u32,
+                                        sigs: *const u8, sig_offsets: *const u64, msgs: *const u8,
+                                        msg_offsets: *const u64, codes_out: *mut u8, bitmap_out: *mut u64) -> c_int;
+    pub fn cess_rsa_verify_digest_batch_device(ctx: *mut cess_bls_ctx, digest: c_int, n: usize,
+                                               d_key_idx: *const u32, d_sigs: *const u8, d_sig_offsets: *const u64,
+                                               d_msgs: *const u8, d_msg_offsets: *const u64, d_codes: *mut u8,
+                                               stream: *mut c_void) -> c_int;
+    pub fn cess_rsa_verify_alg(ctx: *mut cess_bls_ctx, alg: c_int, key_der: *const u8, key_len: usize, format: c_int,
+                               msg: *const u8, msg_len: usize, sig: *const u8, sig_len: usize,
+                               ok_out: *mut c_int) -> c_int;
+    pub fn cess_sha2_batch(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, msgs: *const u8, msg_offsets: *const u64,
+                           out: *mut u8) -> c_int;
 }
 
 pub const CESS_RSA_POLICY_RSA_CRATE: c_int = 0;
 pub const CESS_RSA_POLICY_RING_2048_8192: c_int = 1;
+pub const CESS_RSA_POLICY_RING_3072_8192: c_int = 2;
+pub const CESS_RSA_DIGEST_SHA256: c_int = 0;
+pub const CESS_RSA_DIGEST_SHA384: c_int = 1;
+pub const CESS_RSA_DIGEST_SHA512: c_int = 2;
+pub const CESS_RSA_ALG_2048_8192_SHA256: c_int = 0;
+pub const CESS_RSA_ALG_2048_8192_SHA384: c_int = 1;
+pub const CESS_RSA_ALG_2048_8192_SHA512: c_int = 2;
+pub const CESS_RSA_ALG_3072_8192_SHA384: c_int = 3;
 pub const CESS_RSA_E_UNSUPPORTED: c_int = -10;
 pub const CESS_RSA_KEY_SPKI: c_int = 0;
 pub const CESS_RSA_KEY_PKCS1: c_int = 1;

@@ -390,6 +390,50 @@ impl Verifier {
         Ok(Verdicts { bitmap, codes })
     }
 
+    /// rsa_keys_load under a key policy (ffi::CESS_RSA_POLICY_*: the rsa crate's
+    /// checks, or ring's with a 2048- or 3072-bit floor).
+    pub fn rsa_keys_load_policy(&mut self, ders: &[&[u8]], format: i32, policy: i32) -> Result<Vec<i32>, Error> {
+        let mut data = Vec::new();
+        let o = offsets(ders.iter().copied(), &mut data);
+        let mut st = vec![0 as c_int; ders.len()];
+        check(unsafe {
+            ffi::cess_rsa_keys_load_policy(self.ctx, ders.len(), data.as_ptr(), o.as_ptr(), format as c_int,
+                                           policy as c_int, st.as_mut_ptr())
+        })?;
+        Ok(st.into_iter().map(|x| x as i32).collect())
+    }
+
+    /// RSASSA-PKCS1-v1_5 with SHA-256 / SHA-384 / SHA-512 (`digest`:
+    /// ffi::CESS_RSA_DIGEST_*) over a batch against the loaded key table,
+    /// messages of any length hashed on the GPU; codes as verify_rsa_batch.
+    pub fn verify_rsa_digest_batch(&mut self, digest: i32, key_idx: &[u32], msgs: &[&[u8]],
+                                   sigs: &[&[u8]]) -> Result<Verdicts, Error> {
+        assert!(key_idx.len() == msgs.len() && msgs.len() == sigs.len());
+        let n = key_idx.len();
+        let (mut md, mut sd) = (Vec::new(), Vec::new());
+        let mo = offsets(msgs.iter().copied(), &mut md);
+        let so = offsets(sigs.iter().copied(), &mut sd);
+        let mut codes = vec![0u8; n];
+        let mut bitmap = vec![0u64; (n + 63) / 64];
+        check(unsafe {
+            ffi::cess_rsa_verify_digest_batch(self.ctx, digest as c_int, n, key_idx.as_ptr(), sd.as_ptr(), so.as_ptr(),
+                                              md.as_ptr(), mo.as_ptr(), codes.as_mut_ptr(), bitmap.as_mut_ptr())
+        })?;
+        Ok(Verdicts { bitmap, codes })
+    }
+
+    /// verify_signature(alg, msg, sig) for one of verify_miner_cert's four
+    /// SUPPORTED_SIG_ALGS (`alg`: ffi::CESS_RSA_ALG_*), the key in `format`
+    /// loaded under the algorithm's key policy.
+    pub fn verify_rsa_alg(&mut self, alg: i32, key_der: &[u8], format: i32, msg: &[u8], sig: &[u8]) -> Result<bool, Error> {
+        let mut ok: c_int = 0;
+        check(unsafe {
+            ffi::cess_rsa_verify_alg(self.ctx, alg as c_int, key_der.as_ptr(), key_der.len(), format as c_int,
+                                     msg.as_ptr(), msg.len(), sig.as_ptr(), sig.len(), &mut ok)
+        })?;
+        Ok(ok != 0)
+    }
+
     // --- generators (PrivateKey::public_key / sign, src/lib.rs:226-236) -------
     pub fn public_keys(&mut self, sks: &[[u8; 32]]) -> Result<Vec<[u8; 96]>, Error> {
         let flat: Vec<u8> = sks.iter().flat_map(|k| k.iter().copied()).collect();
