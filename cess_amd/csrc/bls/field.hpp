@@ -593,8 +593,14 @@ CESS_HD void update_de30(s30& d, s30& e, int32_t u, int32_t v, int32_t q, int32_
   ce >>= 30;
 #pragma unroll
   for (int i = 1; i < 13; i++) {
-    cd += (int64_t)u * d.v[i] + (int64_t)v * e.v[i] + (int64_t)c::P30[i] * md;
-    ce += (int64_t)q * d.v[i] + (int64_t)r * e.v[i] + (int64_t)c::P30[i] * me;
+    // one product at a time onto the carried sum: each is a mad whose addend
+    // is the chain (summed apart, the three cost a 64-bit add to join)
+    cd += (int64_t)u * d.v[i];
+    cd += (int64_t)v * e.v[i];
+    cd += (int64_t)c::P30[i] * md;
+    ce += (int64_t)q * d.v[i];
+    ce += (int64_t)r * e.v[i];
+    ce += (int64_t)c::P30[i] * me;
     d.v[i - 1] = (int32_t)cd & M30;
     e.v[i - 1] = (int32_t)ce & M30;
     cd >>= 30;
@@ -612,8 +618,10 @@ CESS_HD void update_fg30(s30& f, s30& g, int32_t u, int32_t v, int32_t q, int32_
   cg >>= 30;
 #pragma unroll
   for (int i = 1; i < 13; i++) {
-    cf += (int64_t)u * f.v[i] + (int64_t)v * g.v[i];
-    cg += (int64_t)q * f.v[i] + (int64_t)r * g.v[i];
+    cf += (int64_t)u * f.v[i];
+    cf += (int64_t)v * g.v[i];
+    cg += (int64_t)q * f.v[i];
+    cg += (int64_t)r * g.v[i];
     f.v[i - 1] = (int32_t)cf & M30;
     g.v[i - 1] = (int32_t)cg & M30;
     cf >>= 30;
