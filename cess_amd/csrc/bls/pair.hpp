@@ -139,8 +139,9 @@ CESS_HD void pair_digits(const fp& a, const fp& b, uint32_t (&xa)[14], uint32_t 
   }
 }
 
-// this lane's component of S a b (a, b: the pair's Fp2 values, inputs < 8p as
-// mul_scaled<S>); result < 2p
+// this lane's component of S a b (a, b: the pair's Fp2 values; components
+// < 2^384 as mul_scaled<S>, whose mads these are -- the callers reach < 8p);
+// result < 2p
 template <uint32_t S>
 CESS_HD fph pmul_scaled(const fph& a0, const fph& b0) {
   static_assert(S >= 1 && S <= 3, "digit bound");
