@@ -4,4 +4,6 @@ from .bls import (  # noqa: F401
     CODE_NAMES, Context, DeserializeError, DeviceUnavailable, InvalidPrivateKey, InvalidPublicKey,
     InvalidSignature, PrivateKey, PublicKey, Result, Signature, Verdicts, default_context, load_library,
     verify_batch, verify_bls_signature,
+    ED25519_CODE_NAMES, ED25519_KEY, ED25519_MISMATCH, ED25519_OK, ED25519_POLICY_RING, ED25519_SIG_LEN,
+    ED25519_SIG_RANGE, verify_ed25519,
 )

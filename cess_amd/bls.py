@@ -63,6 +63,12 @@ EXPORTS = (
 )
 # exported too, outside the cess_bls_ / cess_rsa_ name space that EXPORTS lists
 EXPORTS_OTHER = ("cess_sha256_batch", "cess_sha2_batch")
+# include/cess_ed25519.h (batch Ed25519 under ring's ED25519 rules)
+EXPORTS_ED25519 = ("cess_ed25519_keys_load", "cess_ed25519_verify_batch", "cess_ed25519_verify_batch_device",
+                   "cess_ed25519_verify", "cess_ed25519_stage_stats")
+ED25519_POLICY_RING = 0                                                                 # CESS_ED25519_POLICY_RING
+ED25519_OK, ED25519_SIG_LEN, ED25519_SIG_RANGE, ED25519_KEY, ED25519_MISMATCH = range(5)   # cess_ed25519_code
+ED25519_CODE_NAMES = {0: "OK", 1: "SIG_LEN", 2: "SIG_RANGE", 3: "KEY", 4: "MISMATCH"}
 RSA_E_UNSUPPORTED = -10
 RSA_KEY_SPKI, RSA_KEY_PKCS1 = 0, 1
 RSA_POLICY_RSA_CRATE, RSA_POLICY_RING_2048_8192, RSA_POLICY_RING_3072_8192 = 0, 1, 2   # CESS_RSA_POLICY_*
@@ -192,6 +198,14 @@ def load_library(path: str = LIB_PATH):
             lib.cess_rsa_verify_alg.argtypes = [vp, ctypes.c_int, _u8p, sz, ctypes.c_int, _u8p, sz, _u8p, sz,
                                                 ctypes.POINTER(ctypes.c_int)]
             lib.cess_sha2_batch.argtypes = [vp, ctypes.c_int, sz, _u8p, _u64p, _u8p]
+        if hasattr(lib, "cess_ed25519_verify_batch"):   # (likewise)
+            lib.cess_ed25519_keys_load.argtypes = [vp, sz, _u8p, _u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+            lib.cess_ed25519_verify_batch.argtypes = lib.cess_rsa_verify_batch.argtypes
+            lib.cess_ed25519_verify_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+            lib.cess_ed25519_verify.argtypes = [vp, _u8p, sz, _u8p, sz, _u8p, sz, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int)]
+            lib.cess_ed25519_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p),
+                                                     ctypes.POINTER(ctypes.c_double), _u64p, ctypes.c_int, ctypes.c_int]
         lib.cess_bls_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
                                              _u64p, ctypes.c_int, ctypes.c_int]
         lib.cess_bls_launch_records.argtypes = [vp]
@@ -673,6 +687,52 @@ class Context:
         raw = bytes(out)
         return [raw[w * i:w * (i + 1)] for i in range(n)]
 
+    # --- Ed25519 under ring's ED25519 rules (include/cess_ed25519.h) -------
+    def ed25519_keys_load(self, keys: Sequence[bytes], policy: int = ED25519_POLICY_RING) -> list:
+        """Load the Ed25519 key table (keys of any length; only 32-byte keys that decode load);
+        returns per-key status (0 or E_BAD_KEY)."""
+        k = len(keys)
+        st = (ctypes.c_int * max(k, 1))()
+        self._chk(self._lib.cess_ed25519_keys_load(self._h, k, _buf(b"".join(bytes(x) for x in keys)),
+                                                   _offsets([len(x) for x in keys]), policy, st))
+        return list(st)[:k]
+
+    def ed25519_verify_batch(self, key_idx: Sequence[int], msgs: Sequence[bytes], sigs: Sequence[bytes],
+                             with_bitmap: bool = False):
+        """Codes (ED25519_*) of records (key key_idx[i] of the loaded table, message i, signature i);
+        with_bitmap: (codes, bitmap words)."""
+        n = len(key_idx)
+        idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        bitmap = (ctypes.c_uint64 * max((n + 63) // 64, 1))()
+        self._chk(self._lib.cess_ed25519_verify_batch(self._h, n, idx, _buf(b"".join(sigs)),
+                                                      _offsets([len(x) for x in sigs]), _buf(b"".join(msgs)),
+                                                      _offsets([len(m) for m in msgs]), codes, bitmap))
+        if with_bitmap:
+            return bytes(codes)[:n], list(bitmap)[: (n + 63) // 64]
+        return bytes(codes)[:n]
+
+    def ed25519_verify_batch_device(self, n, d_key_idx, d_sigs, d_sig_offs, d_msgs, d_msg_offs, d_codes, stream=0):
+        self._chk(self._lib.cess_ed25519_verify_batch_device(self._h, n, d_key_idx, d_sigs, d_sig_offs, d_msgs,
+                                                             d_msg_offs, d_codes, stream or None))
+
+    def verify_ed25519(self, key: bytes, msg: bytes, sig: bytes, policy: int = ED25519_POLICY_RING) -> bool:
+        """ring's ED25519.verify(key, msg, sig) as a bool; raises BlsInfraError(E_BAD_KEY) where the
+        key does not load (not 32 bytes, or no point)."""
+        ok = ctypes.c_int()
+        key, msg, sig = bytes(key), bytes(msg), bytes(sig)
+        self._chk(self._lib.cess_ed25519_verify(self._h, _buf(key), len(key), _buf(msg), len(msg), _buf(sig),
+                                                len(sig), policy, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def ed25519_stage_stats(self, reset=True) -> dict:
+        """{kernel: (ms summed over launches, launches)} of the Ed25519 kernels since the last reset."""
+        names = (ctypes.c_char_p * 8)()
+        ms = (ctypes.c_double * 8)()
+        ln = (ctypes.c_uint64 * 8)()
+        k = self._lib.cess_ed25519_stage_stats(self._h, names, ms, ln, 8, 1 if reset else 0)
+        return {names[i].decode(): (ms[i], ln[i]) for i in range(k)}
+
     # --- generator side -------------------------------------------------
     def public_keys_raw(self, sks: bytes) -> bytes:
         """n concatenated 32-byte secret keys -> n concatenated 96-byte keys."""
@@ -888,6 +948,17 @@ def default_context() -> Context:
     if _default is None:
         _default = Context()
     return _default
+
+
+def verify_ed25519(sig: bytes, msg: bytes, key: bytes, ctx: Optional[Context] = None) -> bool:
+    """One Ed25519 record under ring's ED25519 rules (argument order of verify_bls_signature):
+    False for every failure, a key that does not load included."""
+    try:
+        return (ctx or default_context()).verify_ed25519(key, msg, sig)
+    except BlsInfraError as e:
+        if e.status == E_BAD_KEY:
+            return False
+        raise
 
 
 # ---------------------------------------------------------------------------

@@ -18,7 +18,7 @@ using namespace cess_host;
 namespace {
 const char* kStageNames[ST_N] = {"k_decode_sig", "k_decode_pk",    "k_hash",       "k_prepare", "k_miller",
                                  "k_final",      "k_rsa_classify", "k_rsa_verify", "k_group",  "k_sign",
-                                 "k_rsa_digest"};
+                                 "k_rsa_digest", "k_ed25519_keys", "k_ed25519_pack", "k_ed25519_verify"};
 }
 
 extern "C" const char* cess_bls_version(void) { return "cess_amd-bls 0.2 (gfx950)"; }
@@ -210,6 +210,7 @@ extern "C" void cess_bls_ctx_destroy(cess_bls_ctx* c) {
   if (c->stream3) (void)hipStreamDestroy(c->stream3);
   delete c->rlc;
   cess_rsa_state_free(c);
+  cess_ed25519_state_free(c);
   delete c;
 }
 
@@ -722,24 +723,39 @@ extern "C" int cess_bls_hash_to_g1_batch(cess_bls_ctx* c, size_t n, const uint8_
   return gen_batch(c, 2, n, nullptr, msgs, offs, out48);
 }
 
-extern "C" int cess_bls_stage_stats(cess_bls_ctx* c, const char** names, double* ms, uint64_t* launches, int max,
-                                    int reset) {
-  ENTRY(c);
-  int k = std::min(max, (int)ST_N);
-  for (int i = 0; i < k; i++) {
+// stages [first, last) of the context and its sub-contexts; returns their number
+static int stage_range(cess_bls_ctx* c, int first, int last, const char** names, double* ms, uint64_t* launches,
+                       int max, int reset) {
+  int k = std::min(max, last - first);
+  for (int q = 0; q < k; q++) {
+    const int i = first + q;
     double v = c->stage_ms[i];
     uint64_t l = c->stage_launches[i];
     for (cess_bls_ctx* s : c->subs) v += s->stage_ms[i], l += s->stage_launches[i];
-    if (names) names[i] = kStageNames[i];
-    if (ms) ms[i] = v;
-    if (launches) launches[i] = l;
+    if (names) names[q] = kStageNames[i];
+    if (ms) ms[q] = v;
+    if (launches) launches[q] = l;
   }
   if (reset) {
-    for (int i = 0; i < ST_N; i++) c->stage_ms[i] = 0, c->stage_launches[i] = 0;
+    for (int i = first; i < last; i++) c->stage_ms[i] = 0, c->stage_launches[i] = 0;
     for (cess_bls_ctx* s : c->subs)
-      for (int i = 0; i < ST_N; i++) s->stage_ms[i] = 0, s->stage_launches[i] = 0;
+      for (int i = first; i < last; i++) s->stage_ms[i] = 0, s->stage_launches[i] = 0;
   }
-  return ST_N;
+  return last - first;
+}
+
+// the BLS and RSA stages, as before the Ed25519 kernels: those have their own
+// list (cess_ed25519_stage_stats), so this one's names and order stay as they were
+extern "C" int cess_bls_stage_stats(cess_bls_ctx* c, const char** names, double* ms, uint64_t* launches, int max,
+                                    int reset) {
+  ENTRY(c);
+  return stage_range(c, 0, ST_ED25519_KEYS, names, ms, launches, max, reset);
+}
+
+extern "C" int cess_ed25519_stage_stats(cess_bls_ctx* c, const char** names, double* ms, uint64_t* launches, int max,
+                                        int reset) {
+  ENTRY(c);
+  return stage_range(c, ST_ED25519_KEYS, ST_N, names, ms, launches, max, reset);
 }
 
 extern "C" int cess_bls_stage_times(cess_bls_ctx* c, const char** names, double* ms, int max, int reset) {

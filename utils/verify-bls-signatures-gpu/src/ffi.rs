@@ -222,7 +222,31 @@ extern "C" {
                                ok_out: *mut c_int) -> c_int;
     pub fn cess_sha2_batch(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, msgs: *const u8, msg_offsets: *const u64,
                            out: *mut u8) -> c_int;
+
+    // include/cess_ed25519.h: batch Ed25519 under ring's ED25519 rules (NodePublicKey / NodeSignature,
+    // primitives/common/src/lib.rs:73-74); no node host function is wired to it
+    pub fn cess_ed25519_keys_load(ctx: *mut cess_bls_ctx, k: usize, keys: *const u8, key_offsets: *const u64,
+                                  policy: c_int, key_status_out: *mut c_int) -> c_int;
+    pub fn cess_ed25519_verify_batch(ctx: *mut cess_bls_ctx, n: usize, key_idx: *const u32, sigs: *const u8,
+                                     sig_offsets: *const u64, msgs: *const u8, msg_offsets: *const u64,
+                                     codes_out: *mut u8, bitmap_out: *mut u64) -> c_int;
+    pub fn cess_ed25519_verify_batch_device(ctx: *mut cess_bls_ctx, n: usize, d_key_idx: *const u32,
+                                            d_sigs: *const u8, d_sig_offsets: *const u64, d_msgs: *const u8,
+                                            d_msg_offsets: *const u64, d_codes: *mut u8,
+                                            stream: *mut c_void) -> c_int;
+    pub fn cess_ed25519_verify(ctx: *mut cess_bls_ctx, key: *const u8, key_len: usize, msg: *const u8,
+                               msg_len: usize, sig: *const u8, sig_len: usize, policy: c_int,
+                               ok_out: *mut c_int) -> c_int;
+    pub fn cess_ed25519_stage_stats(ctx: *mut cess_bls_ctx, names: *mut *const c_char, ms: *mut f64,
+                                    launches: *mut u64, max: c_int, reset: c_int) -> c_int;
 }
+
+pub const CESS_ED25519_POLICY_RING: c_int = 0;
+pub const CESS_ED25519_OK: u8 = 0;
+pub const CESS_ED25519_SIG_LEN: u8 = 1;
+pub const CESS_ED25519_SIG_RANGE: u8 = 2;
+pub const CESS_ED25519_KEY: u8 = 3;
+pub const CESS_ED25519_MISMATCH: u8 = 4;
 
 pub const CESS_RSA_POLICY_RSA_CRATE: c_int = 0;
 pub const CESS_RSA_POLICY_RING_2048_8192: c_int = 1;
