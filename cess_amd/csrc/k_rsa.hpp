@@ -12,26 +12,55 @@
 // Squarings accumulate the off-diagonal products once and double the column.
 // The host has already rejected wrong signature / message lengths (codes 1, 3);
 // the kernel returns 0 OK, 2 SIG_RANGE (s >= n), 4 MISMATCH.
+// Host-compilable with -DCESS_HOSTEMU (tests/hostemu/rsa_emu.cpp) for the CPU
+// tests of every primitive and of the one-record verifier.
 #pragma once
+#if !defined(CESS_HOSTEMU)
 #include <hip/hip_runtime.h>
+#endif
 
 #include <utility>
 
 #include "kernels.hpp"
 #include "rsa.hpp"
 
+#if defined(CESS_HOSTEMU)
+#define CESS_RSA_D inline
+#define CESS_RSA_UNIFORM(x) (x)
+#else
+#define CESS_RSA_D __device__ __forceinline__
+#define CESS_RSA_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
+#endif
+
 namespace rsa_detail {
 
 constexpr uint32_t M28 = 0x0fffffffu;
 
+// a column accumulator: 64 bits on the device; the host build shadows it in
+// 128 bits and records the largest value a column reached (emu_rsa_col_max)
+#if defined(CESS_HOSTEMU)
+typedef unsigned __int128 col_t;
+inline unsigned __int128 g_col_max = 0;
+inline void col_seen(col_t c) {
+  if (c > g_col_max) g_col_max = c;
+}
+#else
+typedef uint64_t col_t;
+CESS_RSA_D void col_seen(col_t) {}
+#endif
+
 // 0, data-dependent on x: each column's products start after the previous
 // column is complete, so the scheduler cannot hoist a fully unrolled
 // product scan's independent columns and run out of registers
+#if defined(CESS_HOSTEMU)
+inline uint64_t zero_after(col_t) { return 0; }
+#else
 __device__ __forceinline__ uint64_t zero_after(uint64_t x) {
   uint32_t z;
   asm volatile("" : "=v"(z) : "0"(0u), "v"((uint32_t)x));
   return z;
 }
+#endif
 
 template <int L>
 struct Big {
@@ -52,12 +81,12 @@ struct MontCtx {
   uint32_t ninv;
   uint32_t (&m)[L];
   uint32_t (&out)[L];
-  uint64_t acc;
+  col_t acc;
 };
 
 // column K of a * b (SQR: of a^2, off-diagonal products once, then doubled)
 template <int L, bool SQR, int K, int I>
-__device__ __forceinline__ void ab_term(MontCtx<L>& c, uint64_t& col) {
+CESS_RSA_D void ab_term(MontCtx<L>& c, col_t& col) {
   constexpr int J = K - I;
   if constexpr (SQR) {
     if constexpr (J > I && J < L) col += (uint64_t)c.a[I] * c.a[J];
@@ -66,13 +95,13 @@ __device__ __forceinline__ void ab_term(MontCtx<L>& c, uint64_t& col) {
   }
 }
 template <int L, int K, int I>
-__device__ __forceinline__ void mn_term(MontCtx<L>& c) {
+CESS_RSA_D void mn_term(MontCtx<L>& c) {
   constexpr int J = K - I;
   if constexpr (I < K && J >= 0 && J < L) c.acc += (uint64_t)c.m[I] * c.n[J];
 }
 template <int L, bool SQR, int K, int... I>
-__device__ __forceinline__ void column(MontCtx<L>& c, std::integer_sequence<int, I...>) {
-  uint64_t col = zero_after(c.acc);
+CESS_RSA_D void column(MontCtx<L>& c, std::integer_sequence<int, I...>) {
+  col_t col = zero_after(c.acc);
   (ab_term<L, SQR, K, I>(c, col), ...);
   if constexpr (SQR) {
     col <<= 1;
@@ -86,17 +115,18 @@ __device__ __forceinline__ void column(MontCtx<L>& c, std::integer_sequence<int,
   } else {
     c.out[K - L] = (uint32_t)c.acc & M28;
   }
+  col_seen(c.acc);
   c.acc >>= 28;
 }
 template <int L, bool SQR, int K>
-__device__ __forceinline__ void columns(MontCtx<L>& c) {
+CESS_RSA_D void columns(MontCtx<L>& c) {
   column<L, SQR, K>(c, std::make_integer_sequence<int, L>{});
   if constexpr (K + 1 < 2 * L - 1) columns<L, SQR, K + 1>(c);
 }
 
 template <int L, bool SQR>
-__device__ __forceinline__ void mont(const uint32_t (&a)[L], const uint32_t (&b)[L], const uint32_t (&n)[L],
-                                     uint32_t ninv, uint32_t (&out)[L]) {
+CESS_RSA_D void mont(const uint32_t (&a)[L], const uint32_t (&b)[L], const uint32_t (&n)[L], uint32_t ninv,
+                     uint32_t (&out)[L]) {
   uint32_t m[L];
   MontCtx<L> c{a, b, n, ninv, m, out, 0};
   columns<L, SQR, 0>(c);
@@ -105,7 +135,7 @@ __device__ __forceinline__ void mont(const uint32_t (&a)[L], const uint32_t (&b)
 
 // a - n if a >= n (a < 2n)
 template <int L>
-__device__ __forceinline__ void canon(uint32_t (&a)[L], const uint32_t (&n)[L]) {
+CESS_RSA_D void canon(uint32_t (&a)[L], const uint32_t (&n)[L]) {
   uint32_t d[L];
   int32_t borrow = 0;
 #pragma unroll
@@ -120,7 +150,7 @@ __device__ __forceinline__ void canon(uint32_t (&a)[L], const uint32_t (&n)[L]) 
 
 // 28-bit limbs -> W 32-bit words (compile-time shifts)
 template <int L, int W>
-__device__ __forceinline__ void to_words(const uint32_t (&a)[L], uint32_t (&w)[W]) {
+CESS_RSA_D void to_words(const uint32_t (&a)[L], uint32_t (&w)[W]) {
 #pragma unroll
   for (int j = 0; j < W; j++) {
     uint32_t r = 0;
@@ -148,16 +178,15 @@ using namespace rsa_detail;
 // modulus limbs live in SGPRs: the exponentiation keeps 2 L values (x, m) in
 // VGPRs instead of 3 L.  PAD list entries (0xffffffff) are inactive lanes.
 template <int L, bool UNI = false>
-__device__ __forceinline__ void rsa_verify_lane(uint32_t t, uint32_t cnt, const uint32_t* __restrict__ rec,
-                                                const uint32_t* __restrict__ key_idx,
-                                                const RsaKeyDev* __restrict__ keys, const uint8_t* __restrict__ sigs,
-                                                const uint64_t* __restrict__ sig_offs, const uint8_t* __restrict__ msgs,
-                                                const uint64_t* __restrict__ msg_offs, uint32_t* __restrict__ base,
-                                                uint8_t* __restrict__ codes) {
+CESS_RSA_D void rsa_verify_lane(uint32_t t, uint32_t cnt, const uint32_t* __restrict__ rec,
+                                const uint32_t* __restrict__ key_idx, const RsaKeyDev* __restrict__ keys,
+                                const uint8_t* __restrict__ sigs, const uint64_t* __restrict__ sig_offs,
+                                const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_offs,
+                                uint32_t* __restrict__ base, uint8_t* __restrict__ codes) {
   const uint32_t r = rec[t];
   if (r == RSA_PAD) return;
   const uint32_t ki = key_idx[r];
-  const RsaKeyDev& K = keys[UNI ? __builtin_amdgcn_readfirstlane(ki) : ki];
+  const RsaKeyDev& K = keys[UNI ? CESS_RSA_UNIFORM(ki) : ki];
   const int kb = (int)K.k_bytes;
   uint32_t n[L], x[L];
 #pragma unroll
@@ -248,6 +277,7 @@ __device__ __forceinline__ void rsa_verify_lane(uint32_t t, uint32_t cnt, const 
 
 // rec: this class's record list (its length at *cnt, filled by
 // k_rsa_classify or k_rsa_scatter); base: SoA scratch of stride n_max.
+#if !defined(CESS_HOSTEMU)
 #define CESS_RSA_KERNEL(NAME, L, WAVES)                                                                              \
   __global__ __launch_bounds__(256, WAVES) void NAME(                                                                \
       uint32_t n_max, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ rec,                            \
@@ -268,3 +298,4 @@ __device__ __forceinline__ void rsa_verify_lane(uint32_t t, uint32_t cnt, const 
     if (t >= *cnt) return;                                                                                           \
     rsa_verify_lane<L, true>(t, n_max, rec, key_idx, keys, sigs, sig_offs, msgs, msg_offs, base, codes);            \
   }
+#endif

@@ -9,7 +9,11 @@
 // Keys of these sizes are rare (Podr2Key is 2048-bit,
 // primitives/common/src/lib.rs:54): the kernel exists so that every key the
 // reference verifies gets a GPU verdict, not for throughput.
+// tests/hostemu/rsa_big_emu.cpp compiles this file for the host
+// (-DCESS_HOSTEMU) and runs the kernel's body on one record.
+#if !defined(CESS_HOSTEMU)
 #include <hip/hip_runtime.h>
+#endif
 
 #include "kernels.hpp"
 #include "rsa.hpp"

@@ -1,6 +1,7 @@
 // Montgomery product of the loop-form RSA class (k_rsa_big.hip): run-time
-// limb count, 28-bit digits.  Host-compilable with -DCESS_HOSTEMU for the CPU
-// test of the systolic row schedule (tests/test_rsa.py).
+// limb count, 28-bit digits.
+// Host-compilable with -DCESS_HOSTEMU for the CPU tests of the systolic row
+// schedule (tests/test_rsa.py, tests/test_rsa_primitives.py).
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +17,20 @@
 namespace rsa_big {
 
 constexpr uint32_t M28 = 0x0fffffffu;
+
+// a column value u: 64 bits on the device; the host build shadows it in 128
+// bits and records the maximum (emu_rsa_col_max)
+#if defined(CESS_HOSTEMU)
+typedef unsigned __int128 col_t;
+inline unsigned __int128 g_col_max = 0;
+inline uint64_t col_out(col_t c) {
+  if (c > g_col_max) g_col_max = c;
+  return (uint64_t)c;
+}
+#else
+typedef uint64_t col_t;
+CESS_RSA_HD uint64_t col_out(col_t c) { return c; }
+#endif
 
 // out = a b R^-1 mod n, in [0, 2n) for a, b < 2n (4n <= R = 2^(28 L)); out
 // (L + 1 words) must not alias a or b.  FIOS rows (one per digit a_i: m_i from
@@ -38,7 +53,7 @@ CESS_RSA_HD void mont_rt(const uint32_t* a, const uint32_t* b, const uint32_t* _
     for (int r = 0; r < KR; r++) ar[r] = a[i0 + r], c[r] = 0, top[r] = 0, m[r] = 0;
     // interior column of row r: window slot w holds column col's b and n
     auto mid = [&](int r, int w, uint32_t in) -> uint32_t {
-      const uint64_t u = (uint64_t)in + (uint64_t)ar[r] * bw[w] + (uint64_t)m[r] * nw[w] + c[r];
+      const uint64_t u = col_out((col_t)in + (uint64_t)ar[r] * bw[w] + (uint64_t)m[r] * nw[w] + c[r]);
       c[r] = (uint32_t)(u >> 28);
       return (uint32_t)u & M28;
     };
@@ -51,10 +66,10 @@ CESS_RSA_HD void mont_rt(const uint32_t* a, const uint32_t* b, const uint32_t* _
 #pragma unroll
       for (int r = 0; r <= q; r++) {
         if (r == q) {   // column 0
-          uint64_t u = (uint64_t)pass + (uint64_t)ar[r] * bw[0];
+          col_t u = (col_t)pass + (uint64_t)ar[r] * bw[0];
           m[r] = ((uint32_t)u * ninv) & M28;
           u += (uint64_t)m[r] * nw[0];
-          c[r] = (uint32_t)(u >> 28);   // the low 28 bits are zero
+          c[r] = (uint32_t)(col_out(u) >> 28);   // the low 28 bits are zero
         } else {
           pass = mid(r, q - r, pass);
         }
