@@ -3,8 +3,11 @@
 // kernels, and a per-record verify that follows k_ed25519_keys /
 // k_ed25519_verify step by step (the hash is rsa_digest512.hpp's compression
 // over a locally padded buffer).  With -DED25519_EMU_MAIN it is a stand-alone
-// program over a text file of records (the sanitizer run).  Never linked into
-// the product library.
+// program over a text file of records, or (first argument "ops") over a file of
+// primitive operand tables whose results it writes out (the sanitizer runs).
+// emu_edp runs the lane functions of tests/probe/ed25519_probe.hip, the GPU
+// probe's own, in a loop over the lanes (tests/test_ed25519_primitives.py).
+// Never linked into the product library.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -14,6 +17,7 @@
 
 #include "../../cess_amd/csrc/ed25519.hpp"
 #include "../../cess_amd/csrc/rsa_digest512.hpp"
+#include "../probe/ed25519_probe.hip"   // the lane functions and EDP_OPS (no device code under CESS_HOSTEMU)
 
 using namespace ed25519;
 
@@ -147,6 +151,30 @@ int emu_ed_verify(const uint8_t* key, uint64_t key_len, const uint8_t* msg, uint
   return verify_one(key, key_len, msg, msg_len, sig, sig_len);
 }
 
+// one operation of the probe on n lanes: 0, 1 for arguments the lanes' bounds
+// forbid, 2 for an unknown name.  Inactive lanes keep what `out` held.
+int emu_edp(const char* name, uint32_t n, const uint8_t* active, const uint32_t* in, uint32_t* out, const uint32_t* tabs,
+            uint32_t n_tabs) {
+#define X(op, NI, NO, NIDX, T)                                                    \
+  if (!strcmp(name, #op)) {                                                       \
+    if (!edp::args_ok(NI, NIDX, n, active, in, out, tabs, n_tabs)) return 1;      \
+    for (uint32_t i = 0; i < n; i++)                                              \
+      if (active[i]) edp::l_##op(in + (uint64_t)i * NI, out + (uint64_t)i * NO, tabs); \
+    return 0;                                                                     \
+  }
+  EDP_OPS(X)
+#undef X
+  return 2;
+}
+// "name:words in:words out:table indices:threads,..."
+const char* emu_edp_ops() {
+  return ""
+#define X(op, NI, NO, NIDX, T) #op ":" #NI ":" #NO ":" #NIDX ":" #T ","
+      EDP_OPS(X)
+#undef X
+      ;
+}
+
 }  // extern "C"
 
 #if defined(ED25519_EMU_MAIN)
@@ -157,8 +185,39 @@ static std::vector<uint8_t> unhex(const std::string& s) {
   for (size_t i = 0; i + 1 < s.size(); i += 2) out.push_back((uint8_t)strtoul(s.substr(i, 2).c_str(), nullptr, 16));
   return out;
 }
+// ops file: per operation "name n n_in n_out n_tabs", then n * n_in words and
+// n_tabs * 240 words, all decimal; the results go to the output file, n * n_out
+// words per operation, every lane active
+static int run_ops(const char* in_path, const char* out_path) {
+  FILE* f = fopen(in_path, "r");
+  FILE* o = fopen(out_path, "w");
+  if (!f || !o) return 2;
+  char name[64];
+  unsigned n, n_in, n_out, n_tabs;
+  int ops = 0;
+  while (fscanf(f, "%63s %u %u %u %u", name, &n, &n_in, &n_out, &n_tabs) == 5) {
+    std::vector<uint32_t> in((size_t)n * n_in), out((size_t)n * n_out, 0xDEADBEEFu), tabs((size_t)n_tabs * kTableWords);
+    std::vector<uint8_t> active(n, 1);
+    for (auto& w : in)
+      if (fscanf(f, "%u", &w) != 1) return 2;
+    for (auto& w : tabs)
+      if (fscanf(f, "%u", &w) != 1) return 2;
+    const int rc = emu_edp(name, n, active.data(), in.data(), out.data(), n_tabs ? tabs.data() : nullptr, n_tabs);
+    if (rc) {
+      printf("%s: status %d\n", name, rc);
+      return 1;
+    }
+    for (size_t i = 0; i < out.size(); i++) fprintf(o, "%u\n", out[i]);
+    ops++;
+  }
+  fclose(f);
+  fclose(o);
+  printf("%d operations\n", ops);
+  return 0;
+}
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
+  if (!strcmp(argv[1], "ops")) return argc == 4 ? run_ops(argv[2], argv[3]) : 2;
   FILE* f = fopen(argv[1], "r");
   if (!f) return 2;
   static char k[8192], m[8192], s[8192];

@@ -4,8 +4,10 @@ CPU: the plain-Python model (tests/ed25519_model.py) against the two fixtures;
 cess_amd/csrc/ed25519.hpp built for the host (tests/hostemu/ed25519_emu.cpp,
 -DCESS_HOSTEMU, no sanitizer preload) against Python integers and the model; the
 same code as a stand-alone program under the address and undefined-behaviour
-sanitizers; the code-object notes of the new kernels; the Rust declarations and
-the Python constants against the header.
+sanitizers (its record file also takes the crafted rows of
+tests/golden/ring_ed25519_crafted.json, whose codes are ring's own); the
+code-object notes of the new kernels; the Rust declarations and the Python
+constants against the header.
 GPU: the fixtures and generated batches through every entry point.
 """
 import ctypes
@@ -14,6 +16,7 @@ import os
 import random
 import re
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -84,7 +87,8 @@ def _emu():
     src = os.path.join(ROOT, "tests", "hostemu", "ed25519_emu.cpp")
     lib = os.path.join(ROOT, "tests", "hostemu", "libed25519_emu.so")
     hdrs = [os.path.join(ROOT, "cess_amd", "csrc", h) for h in ("ed25519.hpp", "rsa_digest512.hpp", "rsa_digest.hpp",
-                                                                "bls/field.hpp")]
+                                                                "bls/field.hpp", "kernels.hpp")]
+    hdrs.append(os.path.join(ROOT, "tests", "probe", "ed25519_probe.hip"))      # its lane functions (emu_edp)
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCESS_HOSTEMU", "-shared", "-fPIC", src, "-o", lib])
     emu = ctypes.CDLL(lib)
@@ -244,13 +248,28 @@ def test_verify_on_host(emu, ring, edges):
     assert hi.value == 0
 
 
+_san = []
+SAN_ENV = {"ASAN_OPTIONS": "halt_on_error=1:detect_leaks=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"}
+
+
+def san_exe():
+    """The emulator as a stand-alone program (its own main, run as a child process) built with the address
+    and undefined-behaviour sanitizers; built once per test run, in a temporary directory."""
+    if not _san:
+        exe = os.path.join(tempfile.mkdtemp(prefix="ed25519_san_"), "ed25519_san")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-DCESS_HOSTEMU",
+                               "-DED25519_EMU_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               os.path.join(ROOT, "tests", "hostemu", "ed25519_emu.cpp"), "-o", exe])
+        _san.append(exe)
+    return _san[0]
+
+
 def test_verify_under_sanitizers(tmp_path, ring, edges):
-    """The emulator's verify over both fixtures as a stand-alone program (its own main, run as a child
-    process) built with the address and undefined-behaviour sanitizers."""
-    exe = str(tmp_path / "ed25519_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-DCESS_HOSTEMU",
-                           "-DED25519_EMU_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "hostemu", "ed25519_emu.cpp"), "-o", exe])
+    """The emulator's verify over the three fixtures as a stand-alone program under the sanitizers."""
+    exe = san_exe()
+    crafted = [tuple(bytes.fromhex(r[k]) for k in ("key", "msg", "sig")) + (r["code"],)
+               for r in _load("ring_ed25519_crafted.json")["rows"]]
+    assert len(crafted) > 300
     hx = lambda b: b.hex() if b else "-"   # noqa: E731
     recs = str(tmp_path / "records.txt")
     with open(recs, "w") as f:
@@ -259,10 +278,12 @@ def test_verify_under_sanitizers(tmp_path, ring, edges):
             f.write("%s %s %s %d\n" % (hx(key), hx(msg), hx(tamper(sig)), MISMATCH))
         for _, _, key, msg, sig, code in edges["rows"]:
             f.write("%s %s %s %d\n" % (hx(key), hx(msg), hx(sig), code))
-    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+        for key, msg, sig, code in crafted:
+            f.write("%s %s %s %d\n" % (hx(key), hx(msg), hx(sig), code))
+    env = dict(os.environ, **SAN_ENV)
     r = subprocess.run([exe, recs], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "%d records, 0 wrong" % (2 * len(ring) + len(edges["rows"])) in r.stdout
+    assert "%d records, 0 wrong" % (2 * len(ring) + len(edges["rows"]) + len(crafted)) in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 
