@@ -49,6 +49,10 @@ __global__ void k_hash_out(uint64_t, const uint8_t*, const uint64_t*, uint8_t*);
 __global__ void k_group(uint64_t, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint32_t*,
                         const uint32_t*, const uint32_t*, uint64_t, uint8_t*, uint8_t*);
 __global__ void k_codes_bitmap(uint64_t, const uint8_t*, uint64_t*);
+// digests of a batch's messages (k_rsa_digest.hpp; the hashed RSA mode's T_i = DigestInfo || H(msg_i) or the
+// digests alone, Ed25519's SHA-512): SHA-256, and SHA-384 / SHA-512 by the last argument (CESS_RSA_DIGEST_*)
+__global__ void k_rsa_digest(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*);
+__global__ void k_rsa_digest512(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*, int);
 // RLC batch mode (k_rlc.hip)
 __global__ void k_rlc_scale(uint64_t, const uint8_t*, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*,
                             uint64_t, uint32_t*, uint32_t*, uint64_t, uint64_t, uint32_t);

@@ -14,7 +14,6 @@ __global__ void k_ed25519_pack(uint64_t, const uint32_t*, uint32_t, const uint8_
                                const uint8_t*, const uint64_t*, uint8_t*, uint64_t*);
 __global__ void k_ed25519_verify(uint64_t, const uint32_t*, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*,
                                  const uint8_t*, const uint64_t*, const uint8_t*, uint8_t*);
-__global__ void k_rsa_digest512(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*, int);
 
 // per-context Ed25519 key tables: the caller's and a one-key table for cess_ed25519_verify
 struct EdTable {

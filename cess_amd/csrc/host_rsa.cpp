@@ -29,10 +29,6 @@ __global__ void k_rsa_count(uint64_t, const uint32_t*, uint32_t, const RsaKeyDev
 __global__ void k_rsa_scan(uint32_t, const uint32_t*, uint32_t*, uint32_t*);
 __global__ void k_rsa_scatter(uint64_t, const uint32_t*, uint32_t, const RsaKeyDev*, const uint8_t*, const uint64_t*,
                               const uint64_t*, const uint32_t*, uint32_t*, uint32_t*, uint64_t);
-// hashed mode front end (k_rsa_digest.hip): T_i = DigestInfo || SHA-256(msg_i), or the digests alone
-__global__ void k_rsa_digest(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*);
-// its SHA-384 / SHA-512 sibling (k_rsa_digest512.hip); the last argument is CESS_RSA_DIGEST_SHA384 or _SHA512
-__global__ void k_rsa_digest512(uint64_t, const uint8_t*, const uint64_t*, uint8_t*, uint32_t, uint64_t*, int);
 // key-uniform lists when the table has at most this many keys and the batch at
 // least this many records per key (padding each (class, key) segment to a
 // multiple of 64 then costs < 25 % idle lanes in the worst case)
@@ -367,17 +363,12 @@ static size_t t_bytes(int digest) { return 19 + digest_bytes(digest); }
 static size_t digest_records(uint64_t n) { return 64 * (n / 64 + 1); }
 static int digest_run(cess_bls_ctx* c, hipStream_t s, int digest, uint64_t n, const uint8_t* d_msgs,
                       const uint64_t* d_moffs, uint8_t* out, bool prefix, uint64_t* t_offs) {
-  hipEvent_t a;
-  int r = prof_begin(c, s, ST_RSA_DIGEST, &a);
-  if (r) return r;
+  const dim3 grid((unsigned)(n / 64 + 1));
   if (digest == CESS_RSA_DIGEST_SHA256)
-    hipLaunchKernelGGL(k_rsa_digest, dim3((unsigned)(n / 64 + 1)), dim3(64), 0, s, n, d_msgs, d_moffs, out,
-                       prefix ? 1u : 0u, t_offs);
+    LAUNCH(ST_RSA_DIGEST, s, k_rsa_digest, grid, dim3(64), 0, s, n, d_msgs, d_moffs, out, prefix ? 1u : 0u, t_offs);
   else
-    hipLaunchKernelGGL(k_rsa_digest512, dim3((unsigned)(n / 64 + 1)), dim3(64), 0, s, n, d_msgs, d_moffs, out,
-                       prefix ? 1u : 0u, t_offs, digest);
-  r = prof_end(c, s, ST_RSA_DIGEST, a);
-  if (r) return r;
+    LAUNCH(ST_RSA_DIGEST, s, k_rsa_digest512, grid, dim3(64), 0, s, n, d_msgs, d_moffs, out, prefix ? 1u : 0u, t_offs,
+           digest);
   HIPCHK(hipGetLastError());
   return CESS_BLS_OK;
 }

@@ -1,69 +1,15 @@
-// k_rsa_digest: SHA-256 of n independent, variable-length, arbitrarily aligned
-// messages -- the hashed RSA mode's front end (RSASSA-PKCS1-v1_5 with SHA-256,
-// ring's RSA_PKCS1_2048_8192_SHA256).  Record i gets T_i = DigestInfo prefix ||
-// H(msg_i) (51 bytes, stride 51) and t_offs[i] = 51 i, which the unchanged raw
-// RSA path (host_rsa.cpp rsa_run) then takes as its (msgs, msg_offs); with
-// prefix = 0 the 32-byte digests alone (cess_sha256_batch).
-//
-// Layout: one wave per workgroup, one lane per message.  A lane walking its
-// own message with byte loads would make every wave load touch 64 cache lines,
-// so the wave stages cooperatively instead.  Per round it copies the next
-// kRoundBlocks 64-byte blocks of each of its 64 messages into LDS: the 64
-// lanes fetch message m's 64 aligned dwords that cover those 256 bytes with
-// one coalesced load and store them, as fetched, to row m (the message's
-// start, length and shift are scalars of that iteration).  Each lane then
-// reads its own row and turns the raw dwords into big-endian stream words:
-// a byte funnel shift over neighbouring dwords removes the misalignment (the
-// 65th dword it needs at the end of a round comes from one per-lane load), and
-// the blocks that hold the message's end get the SHA padding
-// (rsa_digest.hpp).  It compresses kRoundBlocks blocks per round; state and
-// schedule stay in VGPRs.
-//
-// Chunk size.  State, schedule, a block's raw dwords and a batch of staged
-// loads take about 115 VGPRs, so registers allow 4 waves per SIMD; LDS
-// decides.  A row is 16 kRoundBlocks + 1 dwords: the odd stride puts the 32 lanes of a ds_read_b32 group on 32 different banks when they
-// read word j of their rows (stride 65 = 1 mod 32), and the staging stores of
-// one row are consecutive.  kRoundBlocks = 4 makes one wave load cover one
-// message's 256 contiguous bytes (a full-width coalesced access, message
-// parameters in SGPRs) at 64 x 65 x 4 = 16,640 B per wave: 9 waves per CU of
-// 160 KiB, two per SIMD and one over, so a staging wave (latency-bound) has a
-// compressing wave (VALU-bound) beside it.  Two blocks would double the
-// occupancy but halve the contiguous run and need per-lane message
-// parameters; eight would leave one wave per SIMD.
-//
-// Lanes whose message has ended idle until the longest message of the wave is
-// done: the wave's time is that of its longest message.  A batch with one very
-// long record keeps that record's wave (and only it) busy for
-// len / 64 compressions on a single lane; sorting or splitting such batches is
-// the caller's business.
-//
-// Loads stay inside the dwords that hold message bytes (rsa_digest.hpp); lanes
-// with nothing to fetch read the first dword of msg_offs instead, so the loads
-// are unconditional and a batch of them is in flight at once.  A record whose
-// offsets are not ordered or exceed msg_offs[n] is hashed as empty.
-#include <hip/hip_runtime.h>
-
-#include "rsa_digest.hpp"
-
-namespace {
-
-constexpr int kRoundBlocks = 4;                  // 64-byte blocks per message and round
-constexpr int kRoundWords = 16 * kRoundBlocks;   // = the wave's 64 lanes: one stream word per lane
-constexpr int kRowStride = kRoundWords + 1;      // dwords
-constexpr int kBatch = 8;                        // messages whose loads are issued together
-static_assert(kRoundWords == 64, "one stream word per lane");
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) |
-         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-}
-
-}  // namespace
+// k_rsa_digest: SHA-256 of n messages; T_i = DigestInfo prefix || H(msg_i)
+// (51 bytes) or, with prefix = 0, the 32-byte digests alone
+// (cess_sha256_batch).  Layout, contracts and reasoning, and why the body is
+// written out here and in k_rsa_digest512.hip: k_rsa_digest.hpp.  Four 64-byte
+// blocks per round.
+#include "k_rsa_digest.hpp"
 
 __global__ __launch_bounds__(64) void k_rsa_digest(uint64_t n, const uint8_t* __restrict__ msgs,
                                                    const uint64_t* __restrict__ msg_offs, uint8_t* __restrict__ out,
                                                    uint32_t prefix, uint64_t* __restrict__ t_offs) {
   using namespace rsa_digest;
+  constexpr int kRoundBlocks = 4, kTLen = kPrefixLen + 32;
   __shared__ uint32_t rows[64 * kRowStride];
   const uint32_t lane = threadIdx.x;
   const uint64_t i = (uint64_t)blockIdx.x * 64 + lane;
@@ -75,8 +21,8 @@ __global__ __launch_bounds__(64) void k_rsa_digest(uint64_t n, const uint8_t* __
       len = e - b;
     }
   }
-  if (t_offs && i <= n) t_offs[i] = (uint64_t)kTLen * i;
-  const uint64_t nblk = i < n ? padded_len(len) / 64 : 0;
+  if (t_offs && i <= n) t_offs[i] = (uint64_t)kTLen * i;   // (t_offs comes with prefix only)
+  const uint64_t nblk = i < n ? padded_len<Sha256>(len) / 64 : 0;
   unsigned long long mx = nblk;
 #pragma unroll
   for (int off = 32; off; off >>= 1) {
@@ -128,7 +74,8 @@ __global__ __launch_bounds__(64) void k_rsa_digest(uint64_t n, const uint8_t* __
             blk[j] = __builtin_bswap32((uint32_t)((((uint64_t)r[j + 1] << 32) | r[j]) >> (8 * sh)));
         } else {                        // the message's last bytes and the padding
 #pragma unroll
-          for (int j = 0; j < 16; j++) blk[j] = stream_word(r[j], r[j + 1], sh, avail, 64 * b + 4 * j, len, pos0);
+          for (int j = 0; j < 16; j++)
+            blk[j] = stream_word<Sha256>(r[j], r[j + 1], sh, avail, 64 * b + 4 * j, len, pos0);
         }
         bls::sha256_compress(st, blk);
       }

@@ -1,15 +1,11 @@
-// SHA-384 and SHA-512 of variable-length, arbitrarily aligned messages for the
-// hashed RSA mode (RSASSA-PKCS1-v1_5 with SHA-384 / SHA-512, k_rsa_digest512.hip;
-// ring's RSA_PKCS1_2048_8192_SHA384, _SHA512 and RSA_PKCS1_3072_8192_SHA384):
-// the padded stream of a message as a pure function of (len, position), the
-// assembly of one big-endian 32-bit stream word from the two aligned
-// little-endian dwords that hold its bytes, and the compression function over
-// a 128-byte block given as 32 such words.  Shared by the kernel and the host
-// build of the same code (tests/hostemu/rsa_digest512_emu.cpp).
-//
-// Loads follow rsa_digest.hpp's rule (whole aligned dwords, only dwords that
-// hold a message byte); window_avail, dword_needed and the byte funnel shift
-// are that header's.  The two digests differ in the initial values and in how
+// What is SHA-384's and SHA-512's own in the digest kernels (k_rsa_digest512.hip;
+// ring's RSA_PKCS1_2048_8192_SHA384, _SHA512 and RSA_PKCS1_3072_8192_SHA384,
+// and Ed25519): the DigestInfo prefixes, the initial values, the compression
+// function over a 128-byte block given as 32 big-endian 32-bit stream words,
+// and the hash description Sha512 that hands them to rsa_digest.hpp's message
+// stream and k_rsa_digest.hpp's kernel body.  Shared by the kernel and the
+// host builds of the same code (tests/hostemu/rsa_digest512_emu.cpp,
+// ed25519_emu.cpp).  The two digests differ in the initial values and in how
 // many of the 64 state bytes are output (FIPS 180-4 §5.3.4-5, §6.4-5).
 #pragma once
 #include <stdint.h>
@@ -21,13 +17,11 @@ namespace rsa_digest512 {
 constexpr int kSha384 = 1, kSha512 = 2;   // the `digest` selector (CESS_RSA_DIGEST_*)
 
 // DigestInfo prefixes (RFC 8017 §9.2 note 1): T = prefix || H, 19 + 48 = 67 or 19 + 64 = 83 bytes
-using rsa_digest::kPrefixLen;   // all three SHA-2 DigestInfo prefixes are 19 bytes
+using rsa_digest::kPrefixLen;
 CESS_CONST uint8_t kPrefix384[kPrefixLen] = {0x30, 0x41, 0x30, 0x0d, 0x06, 0x09, 0x60, 0x86, 0x48, 0x01,
                                              0x65, 0x03, 0x04, 0x02, 0x02, 0x05, 0x00, 0x04, 0x30};
 CESS_CONST uint8_t kPrefix512[kPrefixLen] = {0x30, 0x51, 0x30, 0x0d, 0x06, 0x09, 0x60, 0x86, 0x48, 0x01,
                                              0x65, 0x03, 0x04, 0x02, 0x03, 0x05, 0x00, 0x04, 0x40};
-CESS_HD uint32_t digest_len(int digest) { return digest == kSha384 ? 48u : 64u; }
-CESS_HD uint32_t prefix_byte(int digest, int j) { return digest == kSha384 ? kPrefix384[j] : kPrefix512[j]; }
 
 CESS_CONST uint64_t SHA384_IV[8] = {0xcbbb9d5dc1059ed8ull, 0x629a292a367cd507ull, 0x9159015a3070dd17ull,
                                     0x152fecd8f70e5939ull, 0x67332667ffc00b31ull, 0x8eb44a8768581511ull,
@@ -52,55 +46,6 @@ CESS_CONST uint64_t SHA512_K[80] = {
     0xd186b8c721c0c207ull, 0xeada7dd6cde0eb1eull, 0xf57d4f7fee6ed178ull, 0x06f067aa72176fbaull, 0x0a637dc5a2c898a6ull,
     0x113f9804bef90daeull, 0x1b710b35131c471bull, 0x28db77f523047d84ull, 0x32caab7b40c72493ull, 0x3c9ebe0a15c9bebcull,
     0x431d67c49c100d4cull, 0x4cc5d4becb3e42b6ull, 0x597f299cfc657e2aull, 0x5fcb6fab3ad6faecull, 0x6c44198c4a475817ull};
-
-// bytes of the padded stream: msg || 0x80 || 0.. || 128-bit big-endian bit length
-CESS_HD uint64_t padded_len512(uint64_t len) { return (len + 17 + 127) & ~(uint64_t)127; }
-
-// byte `pos` of the padded stream for pos >= len (0 for pos < len: the
-// message's own bytes are not this function's)
-CESS_HD uint32_t pad_byte512(uint64_t len, uint64_t pos) {
-  if (pos < len) return 0;
-  if (pos == len) return 0x80;
-  const uint64_t end = padded_len512(len);
-  if (pos >= end - 8 && pos < end) {
-    // the low 64 bits of the 128-bit bit length 8 len; its high 64 bits are
-    // zero for len < 2^61 bytes (the bound of rsa_digest.hpp)
-    const uint64_t q = end - 1 - pos;   // 0 = least significant byte
-    return (uint32_t)((len << 3) >> (8 * q)) & 0xff;
-  }
-  return 0;
-}
-
-// big-endian word of the padding bytes at stream positions p .. p + 3, byte by byte
-CESS_HD uint32_t pad_word512_bytes(uint64_t len, uint64_t p) {
-  return (pad_byte512(len, p) << 24) | (pad_byte512(len, p + 1) << 16) | (pad_byte512(len, p + 2) << 8) |
-         pad_byte512(len, p + 3);
-}
-
-// the same word for p a multiple of 4, without the per-byte branches: the
-// 0x80 marker if it falls in this word, and the halves of len << 3 in the
-// stream's last two words (the two before them, the length's high 64 bits, are
-// zero); the host build checks it against pad_word512_bytes
-CESS_HD uint32_t pad_word512(uint64_t len, uint64_t p) {
-  const uint64_t end = padded_len512(len), bits = len << 3;
-  uint32_t w = (len >= p && len - p < 4) ? 0x80000000u >> (8 * (uint32_t)(len - p)) : 0u;
-  w |= p + 8 == end ? (uint32_t)(bits >> 32) : 0u;
-  w |= p + 4 == end ? (uint32_t)bits : 0u;
-  return w;
-}
-
-// rsa_digest::stream_word with this stream's padding: the big-endian 32-bit
-// word at position pos0 + off (off a multiple of 4) of the padded stream; lo /
-// hi, sh and avail as there (pos0 a multiple of 128 here)
-CESS_HD uint32_t stream_word512(uint32_t lo, uint32_t hi, uint32_t sh, uint32_t avail, uint32_t off, uint64_t len,
-                                uint64_t pos0) {
-  const uint32_t le = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * sh));   // message bytes off .. off + 3
-  const uint32_t be = __builtin_bswap32(le);
-  if (off + 4 <= avail) return be;
-  const uint32_t cnt = avail > off ? avail - off : 0;   // 0 .. 3 message bytes in this word
-  const uint32_t keep = cnt ? ~(0xffffffffu >> (8 * cnt)) : 0u;
-  return (be & keep) | pad_word512(len, pos0 + off);
-}
 
 // 64-bit rotations and shifts on the 32-bit halves: each half of the result
 // is one 32-bit funnel shift (v_alignbit_b32) of the two input halves, where a
@@ -174,5 +119,14 @@ CESS_HD void sha512_compress(uint64_t (&st)[8], const uint32_t (&blk)[32]) {
 #pragma unroll
   for (int i = 0; i < 8; i++) st[i] += v[i];
 }
+
+struct Sha512 {   // SHA-384 and SHA-512 (FIPS 180-4 §6.4-5): 128-byte blocks, a 128-bit length field
+  using word = uint64_t;
+  static constexpr int kBlockBytes = 128, kLenBytes = 16;
+  static CESS_HD word iv(int digest, int j) { return digest == kSha384 ? SHA384_IV[j] : SHA512_IV[j]; }
+  static CESS_HD uint32_t digest_len(int digest) { return digest == kSha384 ? 48u : 64u; }
+  static CESS_HD uint32_t prefix_byte(int digest, int j) { return digest == kSha384 ? kPrefix384[j] : kPrefix512[j]; }
+  static CESS_HD void compress(word (&st)[8], const uint32_t (&blk)[32]) { sha512_compress(st, blk); }
+};
 
 }  // namespace rsa_digest512

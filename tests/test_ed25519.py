@@ -87,7 +87,7 @@ def _emu():
     src = os.path.join(ROOT, "tests", "hostemu", "ed25519_emu.cpp")
     lib = os.path.join(ROOT, "tests", "hostemu", "libed25519_emu.so")
     hdrs = [os.path.join(ROOT, "cess_amd", "csrc", h) for h in ("ed25519.hpp", "rsa_digest512.hpp", "rsa_digest.hpp",
-                                                                "bls/field.hpp", "kernels.hpp")]
+                                                                "bls/h2c.hpp", "bls/field.hpp", "kernels.hpp")]
     hdrs.append(os.path.join(ROOT, "tests", "probe", "ed25519_probe.hip"))      # its lane functions (emu_edp)
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCESS_HOSTEMU", "-shared", "-fPIC", src, "-o", lib])

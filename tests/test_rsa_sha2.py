@@ -227,6 +227,7 @@ def _emu():
     src = os.path.join(ROOT, "tests", "hostemu", "rsa_digest512_emu.cpp")
     lib = os.path.join(ROOT, "tests", "hostemu", "librsa_digest512_emu.so")
     hdrs = [os.path.join(ROOT, "cess_amd", "csrc", h) for h in ("rsa_digest512.hpp", "rsa_digest.hpp", "bls/h2c.hpp")]
+    hdrs.append(os.path.join(ROOT, "tests", "hostemu", "rsa_digest_emu.hpp"))
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCESS_HOSTEMU", "-shared", "-fPIC", src, "-o", lib])
     emu = ctypes.CDLL(lib)
@@ -402,6 +403,29 @@ def test_gpu_sha2_batch(ctx, ring_digests, dg):
     assert len(rows) == 2 and ctx.sha2_batch(dg, [m for m, _ in rows]) == [out for _, out in rows]
     million = b"a" * 1000000
     assert ctx.sha2_batch(dg, [b"abc", million]) == [h(b"abc").digest(), h(million).digest()]
+
+
+# the padding edges of both block sizes, and the lengths around the 256-byte staging rounds' boundaries,
+# where the carry dword and the round's last word are used
+EDGE_LENGTHS = (0, 1, 55, 56, 63, 64, 111, 112, 119, 120, 127, 128) + tuple(range(247, 266)) + tuple(range(503, 522))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dg", [SHA256, SHA384, SHA512])
+def test_gpu_sha2_batch_round_edges(ctx, dg):
+    """What the three digests share, the message stream: every edge length at every start alignment (a
+    leading filler of 0..3 bytes shifts the whole list), in one batch of more than a wave."""
+    h = HASH[dg]
+    rng = random.Random(6)
+    msgs = []
+    for filler in range(4):
+        msgs.append(bytes(rng.randrange(256) for _ in range(filler)))
+        msgs += [bytes(rng.randrange(256) for _ in range(ln)) for ln in EDGE_LENGTHS]
+    starts = np.cumsum([0] + [len(m) for m in msgs])[:-1]
+    for ln in EDGE_LENGTHS:                          # (the test's own premise)
+        assert {int(s) % 4 for s, m in zip(starts, msgs) if len(m) == ln} >= {0, 1, 2, 3}, ln
+    assert len(msgs) >= 65
+    assert ctx.sha2_batch(dg, msgs) == [h(m).digest() for m in msgs]
 
 
 @pytest.mark.gpu

@@ -201,7 +201,8 @@ def test_key_policy(ring):
 def _emu():
     src = os.path.join(ROOT, "tests", "hostemu", "rsa_digest_emu.cpp")
     lib = os.path.join(ROOT, "tests", "hostemu", "librsa_digest_emu.so")
-    hdrs = [os.path.join(ROOT, "cess_amd", "csrc", "rsa_digest.hpp"), os.path.join(ROOT, "cess_amd", "csrc", "bls", "h2c.hpp")]
+    hdrs = [os.path.join(ROOT, "cess_amd", "csrc", "rsa_digest.hpp"), os.path.join(ROOT, "cess_amd", "csrc", "bls", "h2c.hpp"),
+            os.path.join(ROOT, "tests", "hostemu", "rsa_digest_emu.hpp")]
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCESS_HOSTEMU", "-shared", "-fPIC", src, "-o", lib])
     emu = ctypes.CDLL(lib)
