@@ -674,6 +674,8 @@ def encode(g, rounds, slot):
                         if sub2:
                             fl |= fs
                 if oa[3]:
+                    if oa[1] is not None:   # conj(add_nr(..)) would wrap in the kernel (bls/group.hpp)
+                        raise ValueError("conjugate on a two-slot operand")
                     fl |= 64
                 if k == "mul" and ob[3]:
                     raise ValueError("conjugate on the second operand")

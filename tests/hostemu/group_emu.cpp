@@ -2,9 +2,12 @@
 // (cess_amd/csrc/bls/group_prog.hpp) run on the host with the kernel's own
 // operation body (bls/group.hpp group_eval, -DCESS_HOSTEMU) and the kernel's
 // round semantics (every lane of a round reads before any lane writes), so the
-// entry encoding, the Montgomery constants and the lazy-reduction bounds are
-// checked against the golden Gt bytes without a GPU.  Never linked into the
-// product library.
+// entry encoding and the Montgomery constants are checked against the golden
+// Gt bytes without a GPU.  The golden records are a handful of random
+// residues: they do not check the lazy-reduction bounds, which
+// tests/test_group_primitives.py proves from the operand class maxima and
+// probes at their edges (tests/hostemu/group_probe_emu.cpp).  Never linked
+// into the product library.
 #include <string.h>
 
 #include <vector>
