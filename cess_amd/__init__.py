@@ -6,4 +6,5 @@ from .bls import (  # noqa: F401
     verify_batch, verify_bls_signature,
     ED25519_CODE_NAMES, ED25519_KEY, ED25519_MISMATCH, ED25519_OK, ED25519_POLICY_RING, ED25519_SIG_LEN,
     ED25519_SIG_RANGE, verify_ed25519,
+    ED25519_E_INCONSISTENT, ED25519_SIGN_OK, ED25519_SIGN_SIGNER, Ed25519PrivateKey, sign_ed25519,
 )

@@ -66,6 +66,11 @@ EXPORTS_OTHER = ("cess_sha256_batch", "cess_sha2_batch")
 # include/cess_ed25519.h (batch Ed25519 under ring's ED25519 rules)
 EXPORTS_ED25519 = ("cess_ed25519_keys_load", "cess_ed25519_verify_batch", "cess_ed25519_verify_batch_device",
                    "cess_ed25519_verify", "cess_ed25519_stage_stats")
+# include/cess_ed25519_sign.h (Ed25519 key derivation and signing under ring's Ed25519KeyPair rules)
+EXPORTS_ED25519_SIGN = ("cess_ed25519_signers_load", "cess_ed25519_sign_batch", "cess_ed25519_sign_batch_device",
+                        "cess_ed25519_sign", "cess_ed25519_sign_stage_stats")
+ED25519_E_INCONSISTENT = -12                                                            # CESS_ED25519_E_INCONSISTENT
+ED25519_SIGN_OK, ED25519_SIGN_SIGNER = 0, 1                                             # CESS_ED25519_SIGN_*
 ED25519_POLICY_RING = 0                                                                 # CESS_ED25519_POLICY_RING
 ED25519_OK, ED25519_SIG_LEN, ED25519_SIG_RANGE, ED25519_KEY, ED25519_MISMATCH = range(5)   # cess_ed25519_code
 ED25519_CODE_NAMES = {0: "OK", 1: "SIG_LEN", 2: "SIG_RANGE", 3: "KEY", 4: "MISMATCH"}
@@ -206,6 +211,12 @@ def load_library(path: str = LIB_PATH):
                                                 ctypes.POINTER(ctypes.c_int)]
             lib.cess_ed25519_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p),
                                                      ctypes.POINTER(ctypes.c_double), _u64p, ctypes.c_int, ctypes.c_int]
+        if hasattr(lib, "cess_ed25519_sign_batch"):   # (likewise)
+            lib.cess_ed25519_signers_load.argtypes = [vp, sz, _u8p, _u64p, _u8p, _u8p, ctypes.POINTER(ctypes.c_int)]
+            lib.cess_ed25519_sign_batch.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32), _u8p, _u64p, _u8p, _u8p]
+            lib.cess_ed25519_sign_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+            lib.cess_ed25519_sign.argtypes = [vp, _u8p, sz, _u8p, sz, _u8p, _u8p]
+            lib.cess_ed25519_sign_stage_stats.argtypes = lib.cess_ed25519_stage_stats.argtypes
         lib.cess_bls_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
                                              _u64p, ctypes.c_int, ctypes.c_int]
         lib.cess_bls_launch_records.argtypes = [vp]
@@ -733,6 +744,56 @@ class Context:
         k = self._lib.cess_ed25519_stage_stats(self._h, names, ms, ln, 8, 1 if reset else 0)
         return {names[i].decode(): (ms[i], ln[i]) for i in range(k)}
 
+    # --- Ed25519 signing under ring's Ed25519KeyPair rules (include/cess_ed25519_sign.h) ---
+    def ed25519_signers_load(self, seeds: Sequence[bytes], expected_pubs: Optional[Sequence[bytes]] = None):
+        """Load the signer table from seeds (of any length; only 32-byte seeds load); expected_pubs:
+        the 32-byte key each seed must give.  Returns (public keys, statuses): 0, E_BAD_KEY or
+        ED25519_E_INCONSISTENT per signer; the key of a seed that is not 32 bytes is 32 zero bytes."""
+        k = len(seeds)
+        if expected_pubs is not None and (len(expected_pubs) != k or any(len(p) != 32 for p in expected_pubs)):
+            raise ValueError("expected_pubs: one 32-byte key per seed")
+        st = (ctypes.c_int * max(k, 1))()
+        pubs = (ctypes.c_uint8 * (32 * max(k, 1)))()
+        exp = _buf(b"".join(bytes(p) for p in expected_pubs)) if expected_pubs is not None else None
+        self._chk(self._lib.cess_ed25519_signers_load(self._h, k, _buf(b"".join(bytes(x) for x in seeds)),
+                                                      _offsets([len(x) for x in seeds]), exp, pubs, st))
+        raw = bytes(pubs)
+        return [raw[32 * i:32 * (i + 1)] for i in range(k)], list(st)[:k]
+
+    def ed25519_sign_batch(self, signer_idx: Sequence[int], msgs: Sequence[bytes], with_codes: bool = False):
+        """64-byte signatures of records (signer signer_idx[i] of the loaded table, message i); a record
+        whose signer is missing gets 64 zero bytes and ED25519_SIGN_SIGNER.  with_codes: (signatures, codes)."""
+        n = len(signer_idx)
+        idx = (ctypes.c_uint32 * max(n, 1))(*signer_idx)
+        sigs = (ctypes.c_uint8 * (64 * max(n, 1)))()
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        self._chk(self._lib.cess_ed25519_sign_batch(self._h, n, idx, _buf(b"".join(msgs)),
+                                                    _offsets([len(m) for m in msgs]), sigs, codes))
+        raw = bytes(sigs)
+        out = [raw[64 * i:64 * (i + 1)] for i in range(n)]
+        return (out, bytes(codes)[:n]) if with_codes else out
+
+    def ed25519_sign_batch_device(self, n, d_signer_idx, d_msgs, d_msg_offs, d_sigs_out, d_codes=0, stream=0):
+        self._chk(self._lib.cess_ed25519_sign_batch_device(self._h, n, d_signer_idx, d_msgs, d_msg_offs, d_sigs_out,
+                                                           d_codes or None, stream or None))
+
+    def sign_ed25519(self, seed: bytes, msg: bytes, with_public_key: bool = False):
+        """ring's Ed25519KeyPair::from_seed_unchecked(seed).sign(msg): 64 bytes; raises
+        BlsInfraError(E_BAD_KEY) for a seed that is not 32 bytes.  with_public_key: (signature, key)."""
+        seed, msg = bytes(seed), bytes(msg)
+        sig = (ctypes.c_uint8 * 64)()
+        pub = (ctypes.c_uint8 * 32)()
+        self._chk(self._lib.cess_ed25519_sign(self._h, _buf(seed), len(seed), _buf(msg), len(msg), sig, pub))
+        return (bytes(sig), bytes(pub)) if with_public_key else bytes(sig)
+
+    def ed25519_sign_stage_stats(self, reset=True) -> dict:
+        """{kernel: (ms summed over launches, launches)} of the Ed25519 signer's kernels since the last reset."""
+        names = (ctypes.c_char_p * 8)()
+        ms = (ctypes.c_double * 8)()
+        ln = (ctypes.c_uint64 * 8)()
+        k = self._lib.cess_ed25519_sign_stage_stats(self._h, names, ms, ln, 8, 1 if reset else 0)
+        return {names[i].decode(): (ms[i], ln[i]) for i in range(k)}
+
     # --- generator side -------------------------------------------------
     def public_keys_raw(self, sks: bytes) -> bytes:
         """n concatenated 32-byte secret keys -> n concatenated 96-byte keys."""
@@ -1104,6 +1165,42 @@ class PrivateKey:
 
     def __repr__(self):
         return "PrivateKey(REDACTED)"
+
+
+def sign_ed25519(seed: bytes, msg: bytes, ctx: Optional[Context] = None) -> bytes:
+    """The 64-byte Ed25519 signature of msg under the key pair of a 32-byte seed (ring's
+    Ed25519KeyPair::from_seed_unchecked(seed).sign(msg)); deterministic."""
+    return (ctx or default_context()).sign_ed25519(seed, msg)
+
+
+class Ed25519PrivateKey:
+    """An Ed25519 seed, in the shape of PrivateKey: public_key() and sign() run on the GPU.  Not
+    hardened against side channels on a shared device (include/cess_ed25519_sign.h)."""
+    BYTES = 32
+
+    def __init__(self, seed: bytes, ctx: Optional[Context] = None):
+        seed = bytes(seed)
+        if len(seed) != self.BYTES:
+            raise DeserializeError(InvalidPrivateKey.WrongLength)
+        self._seed = seed
+        self._ctx = ctx
+
+    @classmethod
+    def from_seed(cls, seed: bytes, ctx: Optional[Context] = None) -> "Ed25519PrivateKey":
+        return cls(seed, ctx)
+
+    def public_key(self) -> bytes:
+        """the 32-byte key A"""
+        return (self._ctx or default_context()).sign_ed25519(self._seed, b"", with_public_key=True)[1]
+
+    def sign(self, message: bytes) -> bytes:
+        return (self._ctx or default_context()).sign_ed25519(self._seed, bytes(message))
+
+    def __eq__(self, other):
+        return isinstance(other, Ed25519PrivateKey) and other._seed == self._seed
+
+    def __repr__(self):
+        return "Ed25519PrivateKey(REDACTED)"
 
 
 def verify_bls_signature(sig: bytes, msg: bytes, key: bytes) -> Result:

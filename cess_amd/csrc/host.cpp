@@ -18,7 +18,9 @@ using namespace cess_host;
 namespace {
 const char* kStageNames[ST_N] = {"k_decode_sig", "k_decode_pk",    "k_hash",       "k_prepare", "k_miller",
                                  "k_final",      "k_rsa_classify", "k_rsa_verify", "k_group",  "k_sign",
-                                 "k_rsa_digest", "k_ed25519_keys", "k_ed25519_pack", "k_ed25519_verify"};
+                                 "k_rsa_digest", "k_ed25519_keys", "k_ed25519_pack", "k_ed25519_verify",
+                                 "k_ed25519_comb", "k_ed25519_signers", "k_ed25519_sign_pack", "k_ed25519_sign_r",
+                                 "k_ed25519_sign_s"};
 }
 
 extern "C" const char* cess_bls_version(void) { return "cess_amd-bls 0.2 (gfx950)"; }
@@ -41,6 +43,7 @@ extern "C" const char* cess_bls_status_string(int s) {
     case CESS_BLS_E_BAD_SIG: return "signature does not deserialize (verify_bls would panic)";
     case CESS_BLS_E_NO_COMM: return "no communicator (cess_bls_comm_init / cess_bls_comm_init_shm)";
     case CESS_BLS_E_COMM: return "communicator failed (peer timeout, or the communicator was aborted)";
+    case CESS_ED25519_E_INCONSISTENT: return "Ed25519 public key does not match the seed (ring: inconsistent_components)";
     case CESS_RSA_E_UNSUPPORTED: return "RSA key not supported on the GPU (> 2048-bit, even modulus or non-NULL parameters): the caller's CPU path decides";
   }
   return "unknown status";
@@ -211,6 +214,7 @@ extern "C" void cess_bls_ctx_destroy(cess_bls_ctx* c) {
   delete c->rlc;
   cess_rsa_state_free(c);
   cess_ed25519_state_free(c);
+  cess_ed25519_sign_state_free(c);
   delete c;
 }
 
@@ -755,7 +759,14 @@ extern "C" int cess_bls_stage_stats(cess_bls_ctx* c, const char** names, double*
 extern "C" int cess_ed25519_stage_stats(cess_bls_ctx* c, const char** names, double* ms, uint64_t* launches, int max,
                                         int reset) {
   ENTRY(c);
-  return stage_range(c, ST_ED25519_KEYS, ST_N, names, ms, launches, max, reset);
+  return stage_range(c, ST_ED25519_KEYS, ST_ED25519_COMB, names, ms, launches, max, reset);
+}
+
+// the signer's stages (include/cess_ed25519_sign.h)
+extern "C" int cess_ed25519_sign_stage_stats(cess_bls_ctx* c, const char** names, double* ms, uint64_t* launches,
+                                             int max, int reset) {
+  ENTRY(c);
+  return stage_range(c, ST_ED25519_COMB, ST_N, names, ms, launches, max, reset);
 }
 
 extern "C" int cess_bls_stage_times(cess_bls_ctx* c, const char** names, double* ms, int max, int reset) {

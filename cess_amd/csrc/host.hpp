@@ -2,8 +2,8 @@
 // include/cess_bls.h (host.cpp: per-device context and the per-signature
 // pipeline; host_rlc.cpp: RLC batch mode; host_multi.cpp: RCCL communicator,
 // sharded batches and multi-device contexts; host_rsa.cpp: RSA batches;
-// host_ed25519.cpp: Ed25519 batches; host_service.cpp: deserialize batch and
-// verdict cache): the context, the
+// host_ed25519.cpp: Ed25519 batches; host_ed25519_sign.cpp: the Ed25519 signer;
+// host_service.cpp: deserialize batch and verdict cache): the context, the
 // entry-point and launch macros, the choice of the heavy kernels, message
 // staging and the workers one file defines for another.  The index arithmetic
 // that needs no HIP is in host_pure.hpp.  Not part of the C ABI.
@@ -20,6 +20,7 @@
 #include "../../include/cess_bls.h"
 #include "../../include/cess_rsa.h"
 #include "../../include/cess_ed25519.h"
+#include "../../include/cess_ed25519_sign.h"
 #include "comm.hpp"
 #include "host_pure.hpp"
 #include "kernels.hpp"
@@ -86,7 +87,9 @@ __global__ void k_msm_finish(uint32_t, uint32_t, const uint32_t*, uint32_t*, uin
 namespace cess_host {
 
 enum Stage { ST_DECODE_SIG, ST_DECODE_PK, ST_HASH, ST_PREPARE, ST_MILLER, ST_FINAL, ST_RSA_CLASSIFY, ST_RSA_VERIFY,
-             ST_GROUP, ST_SIGN, ST_RSA_DIGEST, ST_ED25519_KEYS, ST_ED25519_PACK, ST_ED25519_VERIFY, ST_N };
+             ST_GROUP, ST_SIGN, ST_RSA_DIGEST, ST_ED25519_KEYS, ST_ED25519_PACK, ST_ED25519_VERIFY,
+             // the Ed25519 signer's (cess_ed25519_sign_stage_stats)
+             ST_ED25519_COMB, ST_ED25519_SIGNERS, ST_ED25519_SIGN_PACK, ST_ED25519_SIGN_R, ST_ED25519_SIGN_S, ST_N };
 constexpr int kBlock = 256;
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
@@ -169,6 +172,7 @@ struct ProfRec {
 
 struct RsaState;   // host_rsa.cpp
 struct Ed25519State;   // host_ed25519.cpp
+struct Ed25519SignState;   // host_ed25519_sign.cpp
 
 struct cess_bls_ctx {
   int device = 0;
@@ -226,6 +230,8 @@ struct cess_bls_ctx {
   RsaState* rsa = nullptr;
   // Ed25519 key tables and staging (host_ed25519.cpp)
   Ed25519State* ed25519 = nullptr;
+  // Ed25519 signer table, comb table and staging (host_ed25519_sign.cpp)
+  Ed25519SignState* ed25519_sign = nullptr;
 };
 
 #define HIPCHK(x)                                 \
@@ -374,6 +380,9 @@ void cess_rsa_state_free(cess_bls_ctx* c);
 int cess_ed25519_one(cess_bls_ctx* s, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                      const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
 void cess_ed25519_state_free(cess_bls_ctx* c);
+int cess_ed25519_sign_one(cess_bls_ctx* s, size_t n, const uint32_t* signer_idx, const uint8_t* msgs,
+                          const uint64_t* moffs, uint8_t* sigs_out, uint8_t* codes_out);
+void cess_ed25519_sign_state_free(cess_bls_ctx* c);
 // one process, several GPUs (host_multi.cpp)
 int cess_multi_create(const cess_bls_config* cfg, int ndev, cess_bls_ctx* c);
 int cess_multi_verify(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
@@ -396,3 +405,5 @@ int cess_multi_rsa_digest(cess_bls_ctx* c, int digest, size_t n, const uint32_t*
                           uint64_t* bitmap_out);
 int cess_multi_ed25519(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const uint8_t* sigs, const uint64_t* soffs,
                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
+int cess_multi_ed25519_sign(cess_bls_ctx* c, size_t n, const uint32_t* signer_idx, const uint8_t* msgs,
+                            const uint64_t* moffs, uint8_t* sigs_out, uint8_t* codes_out);

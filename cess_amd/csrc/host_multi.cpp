@@ -659,3 +659,15 @@ int cess_multi_ed25519(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const
                             codes_out ? codes_out + b : nullptr, bitmap_out ? bitmap_out + b / 64 : nullptr);
   });
 }
+
+// the Ed25519 signer (host_ed25519_sign.cpp): the same sharding; each device
+// signs its own records from its copy of the signer table
+int cess_multi_ed25519_sign(cess_bls_ctx* c, size_t n, const uint32_t* signer_idx, const uint8_t* msgs,
+                            const uint64_t* moffs, uint8_t* sigs_out, uint8_t* codes_out) {
+  if (n == 0) return CESS_BLS_OK;
+  if (!signer_idx || !moffs || !sigs_out) return CESS_BLS_E_INVALID_ARG;
+  return for_each_shard(c, n, [&](cess_bls_ctx* s, uint64_t b, uint64_t e) {
+    return cess_ed25519_sign_one(s, e - b, signer_idx + b, msgs, moffs + b, sigs_out + 64 * b,
+                                 codes_out ? codes_out + b : nullptr);
+  });
+}

@@ -49,6 +49,7 @@ extern "C" {
 /* (-10 is CESS_RSA_E_UNSUPPORTED, include/cess_rsa.h) */
 #define CESS_BLS_E_COMM (-11)    /* communicator (RCCL or shm): a peer timed out (CESS_BLS_COMM_TIMEOUT_MS) or the
                                     communicator was aborted; every later collective on it fails the same way */
+/* (-12 is CESS_ED25519_E_INCONSISTENT, include/cess_ed25519_sign.h) */
 
 enum cess_bls_code {
   CESS_BLS_CODE_OK = 0,

@@ -14,6 +14,8 @@
 //! verification must not silently degrade).
 
 mod ffi;
+// include/cess_ed25519_sign.h: the Ed25519 signer (declarations and `Verifier` methods)
+pub mod ed25519_sign;
 
 use core::ffi::{c_int, c_void, CStr};
 use std::sync::{Mutex, OnceLock};
