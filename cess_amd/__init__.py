@@ -6,5 +6,7 @@ from .bls import (  # noqa: F401
     verify_batch, verify_bls_signature,
     ED25519_CODE_NAMES, ED25519_KEY, ED25519_MISMATCH, ED25519_OK, ED25519_POLICY_RING, ED25519_SIG_LEN,
     ED25519_SIG_RANGE, verify_ed25519,
+    ECDSA_ALG_P256_SHA256_ASN1, ECDSA_ALG_P256_SHA256_FIXED, ECDSA_ALG_P256_SHA384_ASN1, ECDSA_CODE_NAMES, ECDSA_KEY,
+    ECDSA_MISMATCH, ECDSA_OK, ECDSA_SIG_FORMAT, ECDSA_SIG_RANGE, verify_ecdsa,
     ED25519_E_INCONSISTENT, ED25519_SIGN_OK, ED25519_SIGN_SIGNER, Ed25519PrivateKey, sign_ed25519,
 )

@@ -69,6 +69,12 @@ EXPORTS_ED25519 = ("cess_ed25519_keys_load", "cess_ed25519_verify_batch", "cess_
 # include/cess_ed25519_sign.h (Ed25519 key derivation and signing under ring's Ed25519KeyPair rules)
 EXPORTS_ED25519_SIGN = ("cess_ed25519_signers_load", "cess_ed25519_sign_batch", "cess_ed25519_sign_batch_device",
                         "cess_ed25519_sign", "cess_ed25519_sign_stage_stats")
+# include/cess_ecdsa.h (batch ECDSA P-256 under ring's ECDSA_P256_* rules)
+EXPORTS_ECDSA = ("cess_ecdsa_keys_load", "cess_ecdsa_verify_batch", "cess_ecdsa_verify_batch_device",
+                 "cess_ecdsa_verify", "cess_ecdsa_stage_stats")
+ECDSA_ALG_P256_SHA256_FIXED, ECDSA_ALG_P256_SHA256_ASN1, ECDSA_ALG_P256_SHA384_ASN1 = range(3)   # CESS_ECDSA_ALG_*
+ECDSA_OK, ECDSA_SIG_FORMAT, ECDSA_SIG_RANGE, ECDSA_KEY, ECDSA_MISMATCH = range(5)               # cess_ecdsa_code
+ECDSA_CODE_NAMES = {0: "OK", 1: "SIG_FORMAT", 2: "SIG_RANGE", 3: "KEY", 4: "MISMATCH"}
 ED25519_E_INCONSISTENT = -12                                                            # CESS_ED25519_E_INCONSISTENT
 ED25519_SIGN_OK, ED25519_SIGN_SIGNER = 0, 1                                             # CESS_ED25519_SIGN_*
 ED25519_POLICY_RING = 0                                                                 # CESS_ED25519_POLICY_RING
@@ -211,6 +217,16 @@ def load_library(path: str = LIB_PATH):
                                                 ctypes.POINTER(ctypes.c_int)]
             lib.cess_ed25519_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p),
                                                      ctypes.POINTER(ctypes.c_double), _u64p, ctypes.c_int, ctypes.c_int]
+        if hasattr(lib, "cess_ecdsa_verify_batch"):   # (likewise)
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            lib.cess_ecdsa_keys_load.argtypes = [vp, sz, _u8p, _u64p, ctypes.POINTER(ctypes.c_int)]
+            lib.cess_ecdsa_verify_batch.argtypes = [vp, ctypes.c_int, sz, u32p, _u8p, _u64p, _u8p, _u64p, _u8p, _u64p]
+            lib.cess_ecdsa_verify_batch_device.argtypes = [vp, ctypes.c_int, sz, vp, vp, vp, vp, vp, vp, vp]
+            lib.cess_ecdsa_verify.argtypes = [vp, ctypes.c_int, _u8p, sz, _u8p, sz, _u8p, sz,
+                                              ctypes.POINTER(ctypes.c_int)]
+            lib.cess_ecdsa_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p),
+                                                   ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int]
         if hasattr(lib, "cess_ed25519_sign_batch"):   # (likewise)
             lib.cess_ed25519_signers_load.argtypes = [vp, sz, _u8p, _u64p, _u8p, _u8p, ctypes.POINTER(ctypes.c_int)]
             lib.cess_ed25519_sign_batch.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32), _u8p, _u64p, _u8p, _u8p]
@@ -744,6 +760,52 @@ class Context:
         k = self._lib.cess_ed25519_stage_stats(self._h, names, ms, ln, 8, 1 if reset else 0)
         return {names[i].decode(): (ms[i], ln[i]) for i in range(k)}
 
+    # --- ECDSA P-256 under ring's ECDSA_P256_* rules (include/cess_ecdsa.h) ---
+    def ecdsa_keys_load(self, keys: Sequence[bytes]) -> list:
+        """Load the ECDSA key table (keys of any length; only uncompressed 65-byte points on the curve load);
+        returns per-key status (0 or E_BAD_KEY)."""
+        k = len(keys)
+        st = (ctypes.c_int * max(k, 1))()
+        self._chk(self._lib.cess_ecdsa_keys_load(self._h, k, _buf(b"".join(bytes(x) for x in keys)),
+                                                 _offsets([len(x) for x in keys]), st))
+        return list(st)[:k]
+
+    def ecdsa_verify_batch(self, key_idx: Sequence[int], msgs: Sequence[bytes], sigs: Sequence[bytes],
+                           alg: int = ECDSA_ALG_P256_SHA256_ASN1, with_bitmap: bool = False):
+        """Codes (ECDSA_*) of records (key key_idx[i] of the loaded table, message i, signature i) under
+        algorithm `alg`; with_bitmap: (codes, bitmap words)."""
+        n = len(key_idx)
+        idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        bitmap = (ctypes.c_uint64 * max((n + 63) // 64, 1))()
+        self._chk(self._lib.cess_ecdsa_verify_batch(self._h, alg, n, idx, _buf(b"".join(sigs)),
+                                                    _offsets([len(x) for x in sigs]), _buf(b"".join(msgs)),
+                                                    _offsets([len(m) for m in msgs]), codes, bitmap))
+        if with_bitmap:
+            return bytes(codes)[:n], list(bitmap)[: (n + 63) // 64]
+        return bytes(codes)[:n]
+
+    def ecdsa_verify_batch_device(self, alg, n, d_key_idx, d_sigs, d_sig_offs, d_msgs, d_msg_offs, d_codes, stream=0):
+        self._chk(self._lib.cess_ecdsa_verify_batch_device(self._h, alg, n, d_key_idx, d_sigs, d_sig_offs, d_msgs,
+                                                           d_msg_offs, d_codes, stream or None))
+
+    def verify_ecdsa(self, key: bytes, msg: bytes, sig: bytes, alg: int = ECDSA_ALG_P256_SHA256_ASN1) -> bool:
+        """ring's ECDSA_P256_*.verify(key, msg, sig) as a bool; raises BlsInfraError(E_BAD_KEY) where the
+        key does not load."""
+        ok = ctypes.c_int()
+        key, msg, sig = bytes(key), bytes(msg), bytes(sig)
+        self._chk(self._lib.cess_ecdsa_verify(self._h, alg, _buf(key), len(key), _buf(msg), len(msg), _buf(sig),
+                                              len(sig), ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def ecdsa_stage_stats(self, reset=True) -> dict:
+        """{kernel: (ms summed over launches, launches)} of the ECDSA kernels since the last reset."""
+        names = (ctypes.c_char_p * 8)()
+        ms = (ctypes.c_double * 8)()
+        ln = (ctypes.c_uint64 * 8)()
+        k = self._lib.cess_ecdsa_stage_stats(self._h, names, ms, ln, 8, 1 if reset else 0)
+        return {names[i].decode(): (ms[i], ln[i]) for i in range(k)}
+
     # --- Ed25519 signing under ring's Ed25519KeyPair rules (include/cess_ed25519_sign.h) ---
     def ed25519_signers_load(self, seeds: Sequence[bytes], expected_pubs: Optional[Sequence[bytes]] = None):
         """Load the signer table from seeds (of any length; only 32-byte seeds load); expected_pubs:
@@ -1009,6 +1071,18 @@ def default_context() -> Context:
     if _default is None:
         _default = Context()
     return _default
+
+
+def verify_ecdsa(sig: bytes, msg: bytes, key: bytes, alg: int = ECDSA_ALG_P256_SHA256_ASN1,
+                 ctx: Optional[Context] = None) -> bool:
+    """One ECDSA P-256 record under ring's rules (argument order of verify_bls_signature): False for a
+    key that does not load, as ring's Err(Unspecified)."""
+    try:
+        return (ctx or default_context()).verify_ecdsa(key, msg, sig, alg)
+    except BlsInfraError as e:
+        if e.status == E_BAD_KEY:
+            return False
+        raise
 
 
 def verify_ed25519(sig: bytes, msg: bytes, key: bytes, ctx: Optional[Context] = None) -> bool:

@@ -3,6 +3,7 @@
 // pipeline; host_rlc.cpp: RLC batch mode; host_multi.cpp: RCCL communicator,
 // sharded batches and multi-device contexts; host_rsa.cpp: RSA batches;
 // host_ed25519.cpp: Ed25519 batches; host_ed25519_sign.cpp: the Ed25519 signer;
+// host_ecdsa.cpp: ECDSA P-256 batches;
 // host_service.cpp: deserialize batch and verdict cache): the context, the
 // entry-point and launch macros, the choice of the heavy kernels, message
 // staging and the workers one file defines for another.  The index arithmetic
@@ -21,6 +22,7 @@
 #include "../../include/cess_rsa.h"
 #include "../../include/cess_ed25519.h"
 #include "../../include/cess_ed25519_sign.h"
+#include "../../include/cess_ecdsa.h"
 #include "comm.hpp"
 #include "host_pure.hpp"
 #include "kernels.hpp"
@@ -89,7 +91,9 @@ namespace cess_host {
 enum Stage { ST_DECODE_SIG, ST_DECODE_PK, ST_HASH, ST_PREPARE, ST_MILLER, ST_FINAL, ST_RSA_CLASSIFY, ST_RSA_VERIFY,
              ST_GROUP, ST_SIGN, ST_RSA_DIGEST, ST_ED25519_KEYS, ST_ED25519_PACK, ST_ED25519_VERIFY,
              // the Ed25519 signer's (cess_ed25519_sign_stage_stats)
-             ST_ED25519_COMB, ST_ED25519_SIGNERS, ST_ED25519_SIGN_PACK, ST_ED25519_SIGN_R, ST_ED25519_SIGN_S, ST_N };
+             ST_ED25519_COMB, ST_ED25519_SIGNERS, ST_ED25519_SIGN_PACK, ST_ED25519_SIGN_R, ST_ED25519_SIGN_S,
+             // ECDSA P-256 (cess_ecdsa_stage_stats)
+             ST_ECDSA_KEYS, ST_ECDSA_PACK, ST_ECDSA_VERIFY, ST_N };
 constexpr int kBlock = 256;
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
@@ -173,6 +177,7 @@ struct ProfRec {
 struct RsaState;   // host_rsa.cpp
 struct Ed25519State;   // host_ed25519.cpp
 struct Ed25519SignState;   // host_ed25519_sign.cpp
+struct EcdsaState;   // host_ecdsa.cpp
 
 struct cess_bls_ctx {
   int device = 0;
@@ -232,6 +237,8 @@ struct cess_bls_ctx {
   Ed25519State* ed25519 = nullptr;
   // Ed25519 signer table, comb table and staging (host_ed25519_sign.cpp)
   Ed25519SignState* ed25519_sign = nullptr;
+  // ECDSA P-256 key tables, G's table and staging (host_ecdsa.cpp)
+  EcdsaState* ecdsa = nullptr;
 };
 
 #define HIPCHK(x)                                 \
@@ -383,6 +390,10 @@ void cess_ed25519_state_free(cess_bls_ctx* c);
 int cess_ed25519_sign_one(cess_bls_ctx* s, size_t n, const uint32_t* signer_idx, const uint8_t* msgs,
                           const uint64_t* moffs, uint8_t* sigs_out, uint8_t* codes_out);
 void cess_ed25519_sign_state_free(cess_bls_ctx* c);
+int cess_ecdsa_one(cess_bls_ctx* s, int alg, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                   const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                   uint64_t* bitmap_out);
+void cess_ecdsa_state_free(cess_bls_ctx* c);
 // one process, several GPUs (host_multi.cpp)
 int cess_multi_create(const cess_bls_config* cfg, int ndev, cess_bls_ctx* c);
 int cess_multi_verify(cess_bls_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
@@ -407,3 +418,6 @@ int cess_multi_ed25519(cess_bls_ctx* c, size_t n, const uint32_t* key_idx, const
                        const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out, uint64_t* bitmap_out);
 int cess_multi_ed25519_sign(cess_bls_ctx* c, size_t n, const uint32_t* signer_idx, const uint8_t* msgs,
                             const uint64_t* moffs, uint8_t* sigs_out, uint8_t* codes_out);
+int cess_multi_ecdsa(cess_bls_ctx* c, int alg, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                     const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                     uint64_t* bitmap_out);

@@ -671,3 +671,16 @@ int cess_multi_ed25519_sign(cess_bls_ctx* c, size_t n, const uint32_t* signer_id
                                  codes_out ? codes_out + b : nullptr);
   });
 }
+
+// ECDSA P-256 (host_ecdsa.cpp): the same sharding; each device splits, hashes
+// and verifies its own records against its copy of the key table
+int cess_multi_ecdsa(cess_bls_ctx* c, int alg, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                     const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
+                     uint64_t* bitmap_out) {
+  if (n == 0) return CESS_BLS_OK;
+  if (!key_idx || !soffs || !moffs) return CESS_BLS_E_INVALID_ARG;
+  return for_each_shard(c, n, [&](cess_bls_ctx* s, uint64_t b, uint64_t e) {
+    return cess_ecdsa_one(s, alg, e - b, key_idx + b, sigs, soffs + b, msgs, moffs + b,
+                          codes_out ? codes_out + b : nullptr, bitmap_out ? bitmap_out + b / 64 : nullptr);
+  });
+}

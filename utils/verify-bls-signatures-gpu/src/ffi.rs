@@ -239,7 +239,30 @@ extern "C" {
                                ok_out: *mut c_int) -> c_int;
     pub fn cess_ed25519_stage_stats(ctx: *mut cess_bls_ctx, names: *mut *const c_char, ms: *mut f64,
                                     launches: *mut u64, max: c_int, reset: c_int) -> c_int;
+    // ECDSA P-256 under ring's ECDSA_P256_* rules (include/cess_ecdsa.h)
+    pub fn cess_ecdsa_keys_load(ctx: *mut cess_bls_ctx, k: usize, keys: *const u8, key_offsets: *const u64,
+                                key_status_out: *mut c_int) -> c_int;
+    pub fn cess_ecdsa_verify_batch(ctx: *mut cess_bls_ctx, alg: c_int, n: usize, key_idx: *const u32,
+                                   sigs: *const u8, sig_offsets: *const u64, msgs: *const u8,
+                                   msg_offsets: *const u64, codes_out: *mut u8, bitmap_out: *mut u64) -> c_int;
+    pub fn cess_ecdsa_verify_batch_device(ctx: *mut cess_bls_ctx, alg: c_int, n: usize, d_key_idx: *const u32,
+                                          d_sigs: *const u8, d_sig_offsets: *const u64, d_msgs: *const u8,
+                                          d_msg_offsets: *const u64, d_codes: *mut u8,
+                                          stream: *mut c_void) -> c_int;
+    pub fn cess_ecdsa_verify(ctx: *mut cess_bls_ctx, alg: c_int, key: *const u8, key_len: usize, msg: *const u8,
+                             msg_len: usize, sig: *const u8, sig_len: usize, ok_out: *mut c_int) -> c_int;
+    pub fn cess_ecdsa_stage_stats(ctx: *mut cess_bls_ctx, names: *mut *const c_char, ms: *mut f64,
+                                  launches: *mut u64, max: c_int, reset: c_int) -> c_int;
 }
+
+pub const CESS_ECDSA_ALG_P256_SHA256_FIXED: c_int = 0;
+pub const CESS_ECDSA_ALG_P256_SHA256_ASN1: c_int = 1;
+pub const CESS_ECDSA_ALG_P256_SHA384_ASN1: c_int = 2;
+pub const CESS_ECDSA_OK: u8 = 0;
+pub const CESS_ECDSA_SIG_FORMAT: u8 = 1;
+pub const CESS_ECDSA_SIG_RANGE: u8 = 2;
+pub const CESS_ECDSA_KEY: u8 = 3;
+pub const CESS_ECDSA_MISMATCH: u8 = 4;
 
 pub const CESS_ED25519_POLICY_RING: c_int = 0;
 pub const CESS_ED25519_OK: u8 = 0;

@@ -16,6 +16,8 @@
 mod ffi;
 // include/cess_ed25519_sign.h: the Ed25519 signer (declarations and `Verifier` methods)
 pub mod ed25519_sign;
+// include/cess_ecdsa.h: ECDSA P-256 under ring's rules (`Verifier` methods)
+pub mod ecdsa;
 
 use core::ffi::{c_int, c_void, CStr};
 use std::sync::{Mutex, OnceLock};
