@@ -52,7 +52,10 @@
 // itself; complete formulas (Renes-Costello-Batina, 11 M + 6 mults by
 // constants mixed) would cost three to four multiplies more on every
 // addition.  Nothing here is secret: the branches diverge on crafted inputs
-// only.  Table entries can not be infinite (n is prime and far above 8).
+// only -- which whoever picks the key Q = d G can craft, for any round and
+// either addition (tests/ecdsa_ladder_model.py; DESIGN.md §4 says where each
+// case is tested).  Table entries can not be infinite (n is prime and far
+// above 8).
 //
 // Double multiplication: signed radix-16 digits of u1 and u2 (65 digits, the
 // top one 0 or 1), one ladder of 64 rounds of four doublings sharing both
@@ -129,6 +132,17 @@ CESS_HD void col_seen(col_t c) {
 #else
 typedef uint64_t col_t;
 CESS_HD void col_seen(col_t) {}
+#endif
+
+// pt_madd's special returns.  The host build counts how often each is taken
+// (emu_ecdsa_madd_counts), so that a test row named after one can be held to
+// it; the device build has no counter and no code for it.
+#if defined(CESS_HOSTEMU)
+enum { MADD_INF = 0, MADD_DBL = 1, MADD_CANCEL = 2 };
+inline uint64_t g_madd_seen[3] = {0, 0, 0};
+#define CESS_MADD_SEEN(which) (void)g_madd_seen[which]++
+#else
+#define CESS_MADD_SEEN(which) (void)0
 #endif
 
 CESS_HD fe fe_from(const uint32_t (&k)[10]) {
@@ -531,12 +545,19 @@ CESS_HD jac pt_dbl(const jac& p) {
 
 // p + (x2, y2) for an affine, finite second operand
 CESS_HD jac pt_madd(const jac& p, const fe& x2, const fe& y2) {
-  if (pt_is_inf(p)) return {x2, y2, fe_from(kOneQ)};
+  if (pt_is_inf(p)) {
+    CESS_MADD_SEEN(MADD_INF);
+    return {x2, y2, fe_from(kOneQ)};
+  }
   const fe z1z1 = fe_sqr(p.Z);
   const fe u2 = fe_mul(x2, z1z1), s2 = fe_mul(y2, fe_mul(p.Z, z1z1));
   const fe h = fe_sub(u2, p.X), rr = fe_sub(s2, p.Y);
   if (fe_is_zero(h)) {
-    if (fe_is_zero(rr)) return pt_dbl(p);
+    if (fe_is_zero(rr)) {
+      CESS_MADD_SEEN(MADD_DBL);
+      return pt_dbl(p);
+    }
+    CESS_MADD_SEEN(MADD_CANCEL);
     return pt_infinity();
   }
   const fe hh = fe_sqr(h);

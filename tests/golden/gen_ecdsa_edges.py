@@ -8,6 +8,11 @@ compiled ring code has seen them.  The model itself agrees with every P-256 row
 of ring's vector files (gen_ring_ecdsa.py).
 
 A row: name, alg, key (hex; null: a key index outside the table), msg, sig, code.
+
+The "equal halves" rows (u1 G = u2 Q) are named after a doubling that p256.hpp's
+interleaved ladder does not take: they exercise its final r Z^2 = X test on
+2 u1 G (see the comment at the rows).  Doublings and cancels inside the ladder
+are gen_ecdsa_ladder.py's.
 """
 import json
 import os
@@ -66,6 +71,11 @@ def honest(alg, tag, msg=None, cond=None):
 
 
 # --- the final sum: P + P, P + (-P) -------------------------------------------
+# "Equal halves": u1 G = u2 Q.  A verifier that computes the two multiples apart would double here.  The
+# interleaved ladder of p256.hpp does not: its accumulator is (A_k + B_k e / r) G and never meets an addend, so
+# the first row exercises the final r Z^2 = X test on 2 u1 G, not a doubling branch (the name is kept: the rows
+# are committed).  The opposite-halves row does cancel, at the ladder's very last addition.  Doublings and
+# cancels inside the ladder: gen_ecdsa_ladder.py.
 for alg in range(3):
     msg, e = fresh(alg, "equal halves")
     t = rng.randrange(1, N)

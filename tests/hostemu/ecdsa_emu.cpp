@@ -80,6 +80,15 @@ void emu_ecdsa_col_max(uint64_t* lo, uint64_t* hi, int reset) {
 }
 uint64_t emu_ecdsa_col_bound() { return kColBound; }
 
+// how often pt_madd took each special return since the last reset: an infinite
+// first operand, a doubling, a cancel to infinity (key_table's first addition
+// is a doubling: one per table built)
+void emu_ecdsa_madd_counts(uint64_t* out3, int reset) {
+  for (int i = 0; i < 3; i++) out3[i] = g_madd_seen[i];
+  if (reset)
+    for (int i = 0; i < 3; i++) g_madd_seen[i] = 0;
+}
+
 }  // extern "C"
 
 #if defined(ECDSA_EMU_MAIN)
@@ -116,6 +125,8 @@ int main(int argc, char** argv) {
   }
   fclose(f);
   printf("%d records, %d wrong\n", total, wrong);
+  printf("madd returns: %llu infinite, %llu doubling, %llu cancel\n", (unsigned long long)g_madd_seen[MADD_INF],
+         (unsigned long long)g_madd_seen[MADD_DBL], (unsigned long long)g_madd_seen[MADD_CANCEL]);
   // the primitive rows: "op w0 w1 ..." -> "op o0 o1 ..."
   f = fopen(argv[2], "r");
   FILE* o = fopen(argv[3], "w");

@@ -32,10 +32,14 @@ def load_rows():
             for i, r in enumerate(ring["verify"])]
     rows += [(r["name"], r["alg"], None if r["key"] is None else bytes.fromhex(r["key"]), bytes.fromhex(r["msg"]),
               bytes.fromhex(r["sig"]), r["code"]) for r in edges["rows"]]
-    return ring, edges, rows
+    # valid records whose ladder doubles or cancels at a chosen addition (gen_ecdsa_ladder.py), and their twins
+    ladder = json.load(open(os.path.join(GOLDEN, "ecdsa_ladder.json")))
+    rows += [(r["name"], r["alg"], bytes.fromhex(r["key"]), bytes.fromhex(r["msg"]), bytes.fromhex(r["sig"]), r["code"])
+             for r in ladder["rows"]]
+    return ring, edges, ladder, rows
 
 
-RING, EDGES, ROWS = load_rows()
+RING, EDGES, LADDER, ROWS = load_rows()
 
 
 def digest_of(alg, msg):

@@ -1,5 +1,7 @@
-"""ECDSA P-256 on the GPU (include/cess_ecdsa.h): every fixture row -- ring's 58
-and the crafted ones -- through the host batch, the device batch, the
+"""ECDSA P-256 on the GPU (include/cess_ecdsa.h): every fixture row -- ring's 58,
+the crafted ones and the records that steer the ladder into a doubling or a
+cancel (tests/golden/ecdsa_ladder.json), these also at the wave's edges among
+ordinary and early-leaving records -- through the host batch, the device batch, the
 single-record call and, where the machine has two devices, a two-device
 context; codes and bitmaps exactly; batch sizes around the wave and the block;
 key tables with bad keys in the middle and at both ends; the other families'
@@ -9,8 +11,9 @@ import ctypes
 import numpy as np
 import pytest
 
+import ecdsa_ladder_model as lm
 import ecdsa_model as model
-from test_ecdsa import ROWS
+from test_ecdsa import LADDER, ROWS
 
 pytestmark = pytest.mark.gpu
 OK = model.OK
@@ -125,6 +128,75 @@ def test_batch_sizes(ctx, n):
     codes, words = ctx.ecdsa_verify_batch(idx, msgs, sigs, alg=alg, with_bitmap=True)
     assert list(codes) == want
     assert words == bitmap_of(want) and words[-1] >> ((n - 1) % 64 + 1) == 0
+
+
+EDGE_LANES = (0, 31, 32, 63)
+
+
+def ladder_pool(alg):
+    """the valid records of tests/golden/ecdsa_ladder.json under `alg`, each with the (round, addend, kind) that
+    the ladder takes on it -- traced here on scalars from the fixture's d, not read from its name -- and the twins"""
+    ok, twins = [], []
+    for r in LADDER["rows"]:
+        if r["alg"] != alg:
+            continue
+        row = (r["name"], alg, bytes.fromhex(r["key"]), bytes.fromhex(r["msg"]), bytes.fromhex(r["sig"]), r["code"])
+        assert row in ROWS
+        if r["code"] != OK:
+            twins.append(row)
+            continue
+        rr, ss = (int.from_bytes(b, "big") for b in model.split_sig(alg, row[4]))
+        w = lm.inv(ss)
+        events, _ = lm.trace(model.digest_scalar(alg, row[3]) * w % model.N, rr * w % model.N, int(r["d"], 16))
+        target = (r["round"], r["addend"], r["kind"])
+        assert target in events, r["name"]
+        ok.append((row, target))
+    return ok, twins
+
+
+@pytest.mark.parametrize("n", [64, 65, 257])
+@pytest.mark.parametrize("alg", [0, 1, 2])
+def test_ladder_rows_at_wave_edges_among_ordinary_and_early_rows(ctx, n, alg):
+    """Valid records of tests/golden/ecdsa_ladder.json -- a doubling or a cancel inside the ladder, each traced
+    above to the event it takes -- at lanes 0, 31, 32 and 63 of every wave.  Around them valid ordinary records,
+    the ladder records' twins (one more message byte), and records that leave before the ladder (KEY,
+    SIG_FORMAT).  One batch per rotation of the ladder records over the edge lanes, so that every edge lane of
+    every wave holds every one of them once: both kinds, both additions, rounds 0 and 1, and round 2 under the
+    fixed-length algorithm.  Codes from the fixtures, and the bitmap."""
+    ok, twins = ladder_pool(alg)
+    rest = [r for r in by_alg(alg) if not r[0].startswith("ladder: ")]
+    valid = [r for r in rest if r[5] == OK]
+    early = {code: [r for r in rest if r[5] == code] for code in (model.KEY, model.SIG_FORMAT)}
+    assert len(ok) >= 8 and len(twins) == len(ok) and len(valid) >= 8 and all(early.values())
+    edges = [i for i in range(n) if i % 64 in EDGE_LANES]
+    seen = {i: set() for i in edges}
+    for rot in range(len(ok)):
+        recs = []
+        for i in range(n):
+            if i in seen:
+                row, target = ok[(edges.index(i) + rot) % len(ok)]
+                seen[i].add(target)
+                recs.append(row)
+            elif i % 8 == 1:
+                recs.append(early[model.KEY][(i // 8 + rot) % len(early[model.KEY])])
+            elif i % 8 == 2:
+                recs.append(early[model.SIG_FORMAT][(i // 8 + rot) % len(early[model.SIG_FORMAT])])
+            elif i % 8 == 5:
+                recs.append(twins[(i // 8 + rot) % len(twins)])
+            else:
+                recs.append(valid[(i + rot) % len(valid)])
+        keys, idx, msgs, sigs, want = table_of(recs)
+        assert {OK, model.MISMATCH, model.KEY, model.SIG_FORMAT} <= set(want) and all(want[i] == OK for i in edges)
+        load(ctx, keys)
+        codes, words = ctx.ecdsa_verify_batch(idx, msgs, sigs, alg=alg, with_bitmap=True)
+        assert list(codes) == want, (rot, [(i, r[0]) for i, (r, c) in enumerate(zip(recs, codes)) if c != r[5]])
+        assert words == bitmap_of(want) and words[-1] >> ((n - 1) % 64 + 1) == 0
+        assert list(device_codes(ctx, alg, idx, msgs, sigs)) == want, rot
+    # what every edge lane has held: each (round, addend, kind) of this algorithm's records
+    every = {t for _, t in ok}
+    assert every >= {(k, a, kind) for k in (0, 1) for a in lm.ADDENDS for kind in lm.KINDS}
+    assert alg != model.ALG_P256_SHA256_FIXED or {(2, "Q", "dbl"), (2, "Q", "cancel")} <= every
+    assert {i % 64 for i in edges} == set(EDGE_LANES) and all(seen[i] == every for i in edges)
 
 
 # tables of 1, 3 and 65 keys: a bad key in the middle among good ones, bad keys at both ends around good
