@@ -60,6 +60,9 @@ EXPORTS = (
     "cess_rsa_verify_sha256_batch_device", "cess_rsa_verify_sha256",
     # SHA-384 / SHA-512 and the four algorithms of SUPPORTED_SIG_ALGS
     "cess_rsa_verify_digest_batch", "cess_rsa_verify_digest_batch_device", "cess_rsa_verify_alg",
+    # RSASSA-PSS (ring's RSA_PSS_2048_8192_SHA256 / _SHA384 / _SHA512)
+    "cess_rsa_verify_pss_batch", "cess_rsa_verify_pss_batch_device", "cess_rsa_verify_pss", "cess_rsa_pss_em_batch",
+    "cess_rsa_pss_stage_stats",
 )
 # exported too, outside the cess_bls_ / cess_rsa_ name space that EXPORTS lists
 EXPORTS_OTHER = ("cess_sha256_batch", "cess_sha2_batch")
@@ -209,6 +212,16 @@ def load_library(path: str = LIB_PATH):
             lib.cess_rsa_verify_alg.argtypes = [vp, ctypes.c_int, _u8p, sz, ctypes.c_int, _u8p, sz, _u8p, sz,
                                                 ctypes.POINTER(ctypes.c_int)]
             lib.cess_sha2_batch.argtypes = [vp, ctypes.c_int, sz, _u8p, _u64p, _u8p]
+        if hasattr(lib, "cess_rsa_verify_pss_batch"):   # (likewise)
+            lib.cess_rsa_verify_pss_batch.argtypes = [vp, ctypes.c_int] + lib.cess_rsa_verify_batch.argtypes[1:]
+            lib.cess_rsa_verify_pss_batch_device.argtypes = [vp, ctypes.c_int, sz, vp, vp, vp, vp, vp, vp, vp]
+            lib.cess_rsa_verify_pss.argtypes = [vp, ctypes.c_int, _u8p, sz, ctypes.c_int, _u8p, sz, _u8p, sz,
+                                                ctypes.POINTER(ctypes.c_int)]
+            lib.cess_rsa_pss_em_batch.argtypes = [vp, ctypes.c_int, sz, ctypes.POINTER(ctypes.c_uint32), _u8p, _u64p,
+                                                  _u8p, _u8p]
+            lib.cess_rsa_pss_stage_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p),
+                                                     ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int]
         if hasattr(lib, "cess_ed25519_verify_batch"):   # (likewise)
             lib.cess_ed25519_keys_load.argtypes = [vp, sz, _u8p, _u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
             lib.cess_ed25519_verify_batch.argtypes = lib.cess_rsa_verify_batch.argtypes
@@ -702,6 +715,55 @@ class Context:
         self._chk(self._lib.cess_rsa_verify_alg(self._h, alg, _buf(key_der), len(key_der), fmt, _buf(msg), len(msg),
                                                 _buf(sig), len(sig), ctypes.byref(ok)))
         return bool(ok.value)
+
+    # --- RSASSA-PSS: ring's RSA_PSS_2048_8192_SHA256 / _SHA384 / _SHA512 (include/cess_rsa.h) ---
+    def rsa_verify_pss_batch(self, digest: int, key_idx: Sequence[int], msgs: Sequence[bytes],
+                             sigs: Sequence[bytes], with_bitmap: bool = False):
+        """RSASSA-PSS (salt length = digest length, MGF1 over the same digest) over records of the loaded
+        table, the digest chosen by RSA_DIGEST_*: per-record codes."""
+        n = len(key_idx)
+        idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        bitmap = (ctypes.c_uint64 * max((n + 63) // 64, 1))()
+        self._chk(self._lib.cess_rsa_verify_pss_batch(self._h, digest, n, idx, _buf(b"".join(sigs)),
+                                                      _offsets([len(x) for x in sigs]), _buf(b"".join(msgs)),
+                                                      _offsets([len(m) for m in msgs]), codes, bitmap))
+        if with_bitmap:
+            return bytes(codes)[:n], list(bitmap)[: (n + 63) // 64]
+        return bytes(codes)[:n]
+
+    def rsa_verify_pss_batch_device(self, digest, n, d_key_idx, d_sigs, d_sig_offs, d_msgs, d_msg_offs, d_codes,
+                                    stream=0):
+        self._chk(self._lib.cess_rsa_verify_pss_batch_device(self._h, digest, n, d_key_idx, d_sigs, d_sig_offs,
+                                                             d_msgs, d_msg_offs, d_codes, stream or None))
+
+    def verify_rsa_pss(self, digest: int, key_der: bytes, msg: bytes, sig: bytes, fmt: int = RSA_KEY_SPKI) -> bool:
+        """verify_signature(&RSA_PSS_2048_8192_<digest>, msg, sig) under ring's key policy; raises
+        BlsInfraError(E_BAD_KEY / RSA_E_UNSUPPORTED) for the key."""
+        ok = ctypes.c_int()
+        key_der, msg, sig = bytes(key_der), bytes(msg), bytes(sig)
+        self._chk(self._lib.cess_rsa_verify_pss(self._h, digest, _buf(key_der), len(key_der), fmt, _buf(msg),
+                                                len(msg), _buf(sig), len(sig), ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def rsa_pss_em_batch(self, digest: int, mod_bits: Sequence[int], ems: Sequence[bytes],
+                         digests: Sequence[bytes]) -> bytes:
+        """The EM check alone (k_rsa_pss) over caller-supplied message values m_i (big-endian bytes) of
+        moduli of mod_bits[i] <= 4112 bits and H(msg_i): per-record codes (OK / MISMATCH)."""
+        n = len(ems)
+        bits = (ctypes.c_uint32 * max(n, 1))(*mod_bits)
+        codes = (ctypes.c_uint8 * max(n, 1))()
+        self._chk(self._lib.cess_rsa_pss_em_batch(self._h, digest, n, bits, _buf(b"".join(ems)),
+                                                  _offsets([len(x) for x in ems]), _buf(b"".join(digests)), codes))
+        return bytes(codes)[:n]
+
+    def rsa_pss_stage_stats(self, reset=True) -> dict:
+        """{stage: (ms summed over launches, launches)} of RSASSA-PSS's own stage, k_rsa_pss."""
+        names = (ctypes.c_char_p * 4)()
+        ms = (ctypes.c_double * 4)()
+        ln = (ctypes.c_uint64 * 4)()
+        k = self._lib.cess_rsa_pss_stage_stats(self._h, names, ms, ln, 4, 1 if reset else 0)
+        return {names[i].decode(): (ms[i], ln[i]) for i in range(k)}
 
     def sha2_batch(self, digest: int, msgs: Sequence[bytes]) -> list:
         """SHA-256 / SHA-384 / SHA-512 (RSA_DIGEST_*) of every message: the digest kernels alone."""

@@ -93,7 +93,10 @@ enum Stage { ST_DECODE_SIG, ST_DECODE_PK, ST_HASH, ST_PREPARE, ST_MILLER, ST_FIN
              // the Ed25519 signer's (cess_ed25519_sign_stage_stats)
              ST_ED25519_COMB, ST_ED25519_SIGNERS, ST_ED25519_SIGN_PACK, ST_ED25519_SIGN_R, ST_ED25519_SIGN_S,
              // ECDSA P-256 (cess_ecdsa_stage_stats)
-             ST_ECDSA_KEYS, ST_ECDSA_PACK, ST_ECDSA_VERIFY, ST_N };
+             ST_ECDSA_KEYS, ST_ECDSA_PACK, ST_ECDSA_VERIFY,
+             // RSASSA-PSS's EM check (cess_rsa_pss_stage_stats): over the unsorted class lists, and over
+             // the key-uniform ones, so that the stage tells which list path a call took
+             ST_RSA_PSS, ST_RSA_PSS_U, ST_N };
 constexpr int kBlock = 256;
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }

@@ -24,6 +24,22 @@ RSA_KERNEL_DECL(k_rsa_verify_2048)
 RSA_KERNEL_DECL(k_rsa_verify_2048u)
 __global__ void k_rsa_verify_big(uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const RsaKeyDev*,
                                  const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, uint8_t*);
+// RSASSA-PSS: the 2048-bit and loop-form kernels in store mode (m written out,
+// not compared) and the EM check, one kernel per digest (k_rsa_pss.hip)
+#define RSA_KERNEL_M_DECL(NAME)                                                                                      \
+  __global__ void NAME(uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const RsaKeyDev*, const uint8_t*, \
+                       const uint64_t*, uint32_t*, uint8_t*, uint32_t*);
+RSA_KERNEL_M_DECL(k_rsa_verify_2048m)
+RSA_KERNEL_M_DECL(k_rsa_verify_2048um)
+__global__ void k_rsa_verify_bigm(uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const RsaKeyDev*,
+                                  const uint8_t*, const uint64_t*, uint8_t*, uint32_t*);
+#define RSA_PSS_DECL(NAME)                                                                                            \
+  __global__ void NAME(uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const RsaKeyDev*, const uint32_t*, \
+                       const uint32_t*, const uint32_t*, uint8_t*);
+RSA_PSS_DECL(k_rsa_pss_sha256)
+RSA_PSS_DECL(k_rsa_pss_sha384)
+RSA_PSS_DECL(k_rsa_pss_sha512)
+__global__ void k_rsa_pss_small(uint32_t, const uint32_t*, const uint32_t*, uint8_t*);
 __global__ void k_rsa_count(uint64_t, const uint32_t*, uint32_t, const RsaKeyDev*, const uint8_t*, const uint64_t*,
                             const uint64_t*, uint8_t*, uint32_t*);
 __global__ void k_rsa_scan(uint32_t, const uint32_t*, uint32_t*, uint32_t*);
@@ -172,6 +188,8 @@ void key_row(const std::vector<uint8_t>& mod, uint64_t e, int L, RsaKeyDev& k) {
   memset(&k, 0, sizeof(k));
   k.k_bytes = (uint32_t)mod.size();
   k.limbs = (uint32_t)L;
+  k.mod_bits = 8 * (uint32_t)mod.size();
+  for (uint8_t v = mod[0]; !(v & 0x80); v <<= 1) k.mod_bits--;   // (mod has no leading zero byte: der_uint)
   k.e = e;
   to_limbs(mod, L, k.n28);
   // -n^-1 mod 2^28 (Newton: each step doubles the correct low bits)
@@ -222,7 +240,26 @@ struct RsaState {
   RsaTable user, single;
   DevBuf lists, counts, base, in_idx, in_sigs, in_soffs, in_msgs, in_moffs, out_codes;
   DevBuf t, t_offs;   // hashed mode: T_i at stride 51 / 67 / 83 and its offsets (k_rsa_digest, k_rsa_digest512)
+  // RSASSA-PSS: m = s^e mod n as words (SoA over a class list: kPssWords2048
+  // words per entry of the 2048-bit list, then kPssWordsBig per entry of the
+  // loop-form list) and, for cess_rsa_pss_em_batch, its per-record inputs
+  DevBuf pss_m, pss_bits, pss_list;
 };
+// (the loop-form class holds keys of 8 k + 2 <= 28 RSA_L4096 bits: k <= 514 bytes, 129 words)
+constexpr uint64_t kPssWords2048 = (28 * RSA_L2048 + 31) / 32, kPssWordsBig = (28 * RSA_L4096 + 31) / 32;
+
+// RSASSA-PSS over rsa_run: the digest (a known selector) and H(msg_r) at the
+// digest's stride, as digest_run(prefix = false) writes them
+struct PssRun {
+  int digest;
+  const uint32_t* digests;
+};
+typedef void (*PssKernel)(uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const RsaKeyDev*,
+                          const uint32_t*, const uint32_t*, const uint32_t*, uint8_t*);
+static PssKernel pss_kernel(int digest) {
+  return digest == CESS_RSA_DIGEST_SHA256 ? k_rsa_pss_sha256
+         : digest == CESS_RSA_DIGEST_SHA384 ? k_rsa_pss_sha384 : k_rsa_pss_sha512;
+}
 
 static RsaState& rsa_state(cess_bls_ctx* c) {
   if (!c->rsa) c->rsa = new RsaState();
@@ -277,7 +314,7 @@ static int load_table(cess_bls_ctx* c, RsaTable& T, size_t k, const uint8_t* der
 // device-resident records against table T, enqueued on s
 static int rsa_run(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, const uint32_t* d_idx,
                    const uint8_t* d_sigs, const uint64_t* d_soffs, const uint8_t* d_msgs, const uint64_t* d_moffs,
-                   uint8_t* d_codes) {
+                   uint8_t* d_codes, const PssRun* pss = nullptr) {
   if (n == 0) return CESS_BLS_OK;
   if (n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
   RsaState& S = rsa_state(c);
@@ -307,6 +344,27 @@ static int rsa_run(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, cons
     if (r) return r;
     const uint32_t* L = S.lists.as<uint32_t>();
     uint32_t* B = S.base.as<uint32_t>();
+    if (pss) {   // m of the 2048-bit list, then the EM check; the 1024-bit list's records get RSA_KEY
+      if (S.pss_m.ensure(cap * kPssWords2048 * 4)) return CESS_BLS_E_OOM;
+      uint32_t* M = S.pss_m.as<uint32_t>();
+      r = prof_begin(c, s, ST_RSA_VERIFY, &a);
+      if (r) return r;
+      hipLaunchKernelGGL(k_rsa_verify_2048um, dim3(grid_for(cap)), dim3(kBlock), 0, s, (uint32_t)cap,
+                         (const uint32_t*)(totals + 1), L + cap, d_idx, K, d_sigs, d_soffs, B, d_codes, M);
+      r = prof_end(c, s, ST_RSA_VERIFY, a);
+      if (r) return r;
+      r = prof_begin(c, s, ST_RSA_PSS_U, &a);
+      if (r) return r;
+      hipLaunchKernelGGL(pss_kernel(pss->digest), dim3(grid_for(cap)), dim3(kBlock), 0, s, (uint32_t)cap,
+                         (const uint32_t*)(totals + 1), L + cap, d_idx, K, (const uint32_t*)nullptr,
+                         (const uint32_t*)M, pss->digests, d_codes);
+      hipLaunchKernelGGL(k_rsa_pss_small, dim3(grid_for(cap)), dim3(kBlock), 0, s, (uint32_t)cap,
+                         (const uint32_t*)totals, L, d_codes);
+      r = prof_end(c, s, ST_RSA_PSS_U, a);
+      if (r) return r;
+      HIPCHK(hipGetLastError());
+      return CESS_BLS_OK;
+    }
     r = prof_begin(c, s, ST_RSA_VERIFY, &a);
     if (r) return r;
     hipLaunchKernelGGL(k_rsa_verify_2048u, dim3(grid_for(cap)), dim3(kBlock), 0, s, (uint32_t)cap,
@@ -333,6 +391,31 @@ static int rsa_run(cess_bls_ctx* c, RsaTable& T, hipStream_t s, uint64_t n, cons
   const uint32_t* cnt = S.counts.as<uint32_t>();
   const uint32_t* L = S.lists.as<uint32_t>();
   uint32_t* B = S.base.as<uint32_t>();
+  if (pss) {   // as above, with the loop-form list's m after the 2048-bit list's
+    if (S.pss_m.ensure(n * (kPssWords2048 + (T.big ? kPssWordsBig : 0)) * 4)) return CESS_BLS_E_OOM;
+    uint32_t *M = S.pss_m.as<uint32_t>(), *MB = M + n * kPssWords2048;
+    r = prof_begin(c, s, ST_RSA_VERIFY, &a);
+    if (r) return r;
+    hipLaunchKernelGGL(k_rsa_verify_2048m, dim3(grid_for(n)), dim3(kBlock), 0, s, (uint32_t)n, cnt + 1, L + n, d_idx, K,
+                       d_sigs, d_soffs, B, d_codes, M);
+    if (T.big)
+      hipLaunchKernelGGL(k_rsa_verify_bigm, dim3(grid_for(n)), dim3(kBlock), 0, s, (uint32_t)n, cnt + 2, L + 2 * n,
+                         d_idx, K, d_sigs, d_soffs, d_codes, MB);
+    r = prof_end(c, s, ST_RSA_VERIFY, a);
+    if (r) return r;
+    r = prof_begin(c, s, ST_RSA_PSS, &a);
+    if (r) return r;
+    hipLaunchKernelGGL(pss_kernel(pss->digest), dim3(grid_for(n)), dim3(kBlock), 0, s, (uint32_t)n, cnt + 1, L + n,
+                       d_idx, K, (const uint32_t*)nullptr, (const uint32_t*)M, pss->digests, d_codes);
+    if (T.big)
+      hipLaunchKernelGGL(pss_kernel(pss->digest), dim3(grid_for(n)), dim3(kBlock), 0, s, (uint32_t)n, cnt + 2,
+                         L + 2 * n, d_idx, K, (const uint32_t*)nullptr, (const uint32_t*)MB, pss->digests, d_codes);
+    hipLaunchKernelGGL(k_rsa_pss_small, dim3(grid_for(n)), dim3(kBlock), 0, s, (uint32_t)n, cnt, L, d_codes);
+    r = prof_end(c, s, ST_RSA_PSS, a);
+    if (r) return r;
+    HIPCHK(hipGetLastError());
+    return CESS_BLS_OK;
+  }
   // every class kernel covers n lanes; lanes past the class's count exit
   r = prof_begin(c, s, ST_RSA_VERIFY, &a);
   if (r) return r;
@@ -388,8 +471,29 @@ static int rsa_run_sha256(cess_bls_ctx* c, RsaTable& T, hipStream_t s, int diges
   return rsa_run(c, T, s, n, d_idx, d_sigs, d_soffs, S.t.as<uint8_t>(), S.t_offs.as<uint64_t>(), d_codes);
 }
 
-// digest: a CESS_RSA_DIGEST_* selector for the hashed mode, kRawMode for the raw one
-constexpr int kRawMode = -1;
+// RSASSA-PSS: H(msg_i) alone into the context's buffer (the digest kernels with
+// prefix = false), the exponentiation in store mode and the EM check.  The
+// front end's length checks see empty messages (all-zero offsets), so
+// RSA_MSG_LEN is never produced; the store-mode kernels read no message.
+static int rsa_run_pss(cess_bls_ctx* c, RsaTable& T, hipStream_t s, int digest, uint64_t n, const uint32_t* d_idx,
+                       const uint8_t* d_sigs, const uint64_t* d_soffs, const uint8_t* d_msgs, const uint64_t* d_moffs,
+                       uint8_t* d_codes) {
+  if (n == 0) return CESS_BLS_OK;
+  if (n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
+  RsaState& S = rsa_state(c);
+  const size_t h = digest_bytes(digest);
+  if (S.t.ensure(digest_records(n) * h) | S.t_offs.ensure((n + 1) * 8)) return CESS_BLS_E_OOM;
+  int r = digest_run(c, s, digest, n, d_msgs, d_moffs, S.t.as<uint8_t>(), false, nullptr);
+  if (r) return r;
+  HIPCHK(hipMemsetAsync(S.t_offs.p, 0, (n + 1) * 8, s));
+  const PssRun pss{digest, S.t.as<uint32_t>()};
+  return rsa_run(c, T, s, n, d_idx, d_sigs, d_soffs, nullptr, S.t_offs.as<uint64_t>(), d_codes, &pss);
+}
+
+// digest: a CESS_RSA_DIGEST_* selector for the hashed mode, kRawMode for the
+// raw one, kPssMode + selector for RSASSA-PSS (the shard helpers of
+// host_multi.cpp pass it through)
+constexpr int kRawMode = -1, kPssMode = 0x100;
 static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
                     const uint64_t* soffs, const uint8_t* msgs, const uint64_t* moffs, uint8_t* codes_out,
                     uint64_t* bitmap_out, int digest = kRawMode) {
@@ -416,6 +520,10 @@ static int rsa_host(cess_bls_ctx* c, RsaTable& T, size_t n, const uint32_t* key_
   if (digest == kRawMode)
     r = rsa_run(c, T, s, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(), S.in_soffs.as<uint64_t>(),
                 S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(), S.out_codes.as<uint8_t>());
+  else if (digest >= kPssMode)
+    r = rsa_run_pss(c, T, s, digest - kPssMode, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(),
+                    S.in_soffs.as<uint64_t>(), S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(),
+                    S.out_codes.as<uint8_t>());
   else
     r = rsa_run_sha256(c, T, s, digest, n, S.in_idx.as<uint32_t>(), S.in_sigs.as<uint8_t>(),
                        S.in_soffs.as<uint64_t>(), S.in_msgs.as<uint8_t>(), S.in_moffs.as<uint64_t>(),
@@ -668,4 +776,114 @@ extern "C" int cess_rsa_verify(cess_bls_ctx* c, const uint8_t* key_der, size_t k
   if (r) return r;
   *ok_out = code == RSA_OK;
   return CESS_BLS_OK;
+}
+
+// --- RSASSA-PSS: ring's RSA_PSS_2048_8192_SHA256 / _SHA384 / _SHA512 -----------
+extern "C" int cess_rsa_verify_pss_batch(cess_bls_ctx* c, int digest, size_t n, const uint32_t* key_idx,
+                                         const uint8_t* sigs, const uint64_t* sig_offsets, const uint8_t* msgs,
+                                         const uint64_t* msg_offsets, uint8_t* codes_out, uint64_t* bitmap_out) {
+  ENTRY(c);
+  if (!digest_bytes(digest)) return CESS_BLS_E_INVALID_ARG;
+  if (!c->subs.empty())
+    return cess_multi_rsa_digest(c, kPssMode + digest, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out,
+                                 bitmap_out);
+  return rsa_host(c, rsa_state(c).user, n, key_idx, sigs, sig_offsets, msgs, msg_offsets, codes_out, bitmap_out,
+                  kPssMode + digest);
+}
+
+extern "C" int cess_rsa_verify_pss_batch_device(cess_bls_ctx* c, int digest, size_t n, const uint32_t* d_key_idx,
+                                                const uint8_t* d_sigs, const uint64_t* d_sig_offsets,
+                                                const uint8_t* d_msgs, const uint64_t* d_msg_offsets, uint8_t* d_codes,
+                                                void* stream) {
+  ENTRY(c);
+  if (!digest_bytes(digest) || !c->subs.empty() ||
+      (n && (!d_key_idx || !d_sig_offsets || !d_msg_offsets || !d_codes)))
+    return CESS_BLS_E_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  int r = order_begin(c, s);
+  if (r) return r;
+  r = rsa_run_pss(c, rsa_state(c).user, s, digest, n, d_key_idx, d_sigs, d_sig_offsets, d_msgs, d_msg_offsets,
+                  d_codes);
+  if (r) return r;
+  return call_end(c, s);
+}
+
+extern "C" int cess_rsa_verify_pss(cess_bls_ctx* c, int digest, const uint8_t* key_der, size_t key_len, int format,
+                                   const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len,
+                                   int* ok_out) {
+  ENTRY(c);
+  if (!digest_bytes(digest)) return CESS_BLS_E_INVALID_ARG;
+  if (!ok_out || (!key_der && key_len) || (!msg && msg_len) || (!sig && sig_len)) return CESS_BLS_E_INVALID_ARG;
+  if (format != CESS_RSA_KEY_SPKI && format != CESS_RSA_KEY_PKCS1) return CESS_BLS_E_INVALID_ARG;
+  *ok_out = 0;
+  cess_bls_ctx* d = c->subs.empty() ? c : c->subs[0];
+  static const uint8_t zero = 0;
+  const uint64_t ko[2] = {0, key_len};
+  int st = CESS_BLS_OK;
+  RsaTable& T = rsa_state(d).single;
+  int r = load_table(d, T, 1, key_der ? key_der : &zero, ko, format, &st, CESS_RSA_POLICY_RING_2048_8192);
+  if (r) return r;
+  if (st) return st;   // ring rejects the key (BAD_KEY) or the GPU cannot verify it (UNSUPPORTED)
+  const uint32_t idx = 0;
+  const uint64_t so[2] = {0, sig_len}, mo[2] = {0, msg_len};
+  uint8_t code = 0xff;
+  r = rsa_host(d, T, 1, &idx, sig ? sig : &zero, so, msg ? msg : &zero, mo, &code, nullptr, kPssMode + digest);
+  if (r) return r;
+  *ok_out = code == RSA_OK;
+  return CESS_BLS_OK;
+}
+
+// k_rsa_pss alone over caller-supplied m (test-only, like cess_sha2_batch)
+extern "C" int cess_rsa_pss_em_batch(cess_bls_ctx* c, int digest, size_t n, const uint32_t* mod_bits,
+                                     const uint8_t* ems, const uint64_t* em_offsets, const uint8_t* digests,
+                                     uint8_t* codes_out) {
+  ENTRY(c);
+  const size_t h = digest_bytes(digest);
+  if (!h) return CESS_BLS_E_INVALID_ARG;
+  if (n == 0) return CESS_BLS_OK;
+  if (!mod_bits || !em_offsets || !digests || !codes_out || n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
+  // ring reads m to its end: a length other than k is a mismatch, decided here;
+  // the others are the kernel's list, with m as words (word j of record r at j n + r)
+  std::vector<uint8_t> codes(n, RSA_MISMATCH);
+  std::vector<uint32_t> list, m((size_t)kPssWordsBig * n, 0);
+  for (size_t r = 0; r < n; r++) {
+    if (mod_bits[r] == 0 || mod_bits[r] > 32 * kPssWordsBig - 16 || em_offsets[r + 1] < em_offsets[r]) return CESS_BLS_E_INVALID_ARG;
+    const uint64_t len = em_offsets[r + 1] - em_offsets[r], k = (mod_bits[r] + 7) / 8;
+    if (len != k) continue;
+    if (!ems) return CESS_BLS_E_INVALID_ARG;
+    const uint8_t* em = ems + em_offsets[r];
+    for (uint64_t i = 0; i < k; i++) m[(i >> 2) * n + r] |= (uint32_t)em[k - 1 - i] << (8 * (i & 3));
+    list.push_back((uint32_t)r);
+  }
+  const uint32_t cnt = (uint32_t)list.size();
+  list.push_back(cnt);   // the list's length rides behind it
+  cess_bls_ctx* d = c->subs.empty() ? c : c->subs[0];
+  RsaState& S = rsa_state(d);
+  HIPCHK(hipSetDevice(d->device));
+  hipStream_t s = d->stream;
+  int r = order_begin(d, s);
+  if (r) return r;
+  if (S.pss_m.ensure(m.size() * 4) | S.pss_bits.ensure(n * 4) | S.pss_list.ensure(list.size() * 4) |
+      S.t.ensure(n * h) | S.out_codes.ensure(n))
+    return CESS_BLS_E_OOM;
+  HIPCHK(hipMemcpyAsync(S.pss_m.p, m.data(), m.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(S.pss_bits.p, mod_bits, n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(S.pss_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(S.t.p, digests, n * h, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(S.out_codes.p, codes.data(), n, hipMemcpyHostToDevice, s));
+  const uint32_t* L = S.pss_list.as<uint32_t>();
+  hipEvent_t a;
+  r = prof_begin(d, s, ST_RSA_PSS, &a);
+  if (r) return r;
+  hipLaunchKernelGGL(pss_kernel(digest), dim3(grid_for(n)), dim3(kBlock), 0, s, (uint32_t)n, L + cnt, L,
+                     (const uint32_t*)nullptr, (const RsaKeyDev*)nullptr,
+                     (const uint32_t*)S.pss_bits.as<uint32_t>(), (const uint32_t*)S.pss_m.as<uint32_t>(),
+                     (const uint32_t*)S.t.as<uint32_t>(), S.out_codes.as<uint8_t>());
+  r = prof_end(d, s, ST_RSA_PSS, a);
+  if (r) return r;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(codes_out, S.out_codes.p, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return call_end(d, s);
 }

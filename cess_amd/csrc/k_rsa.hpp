@@ -177,12 +177,17 @@ using namespace rsa_detail;
 // k_rsa_scatter), so the key row is read through a wave-uniform index and the
 // modulus limbs live in SGPRs: the exponentiation keeps 2 L values (x, m) in
 // VGPRs instead of 3 L.  PAD list entries (0xffffffff) are inactive lanes.
-template <int L, bool UNI = false>
+// STORE (RSASSA-PSS, k_rsa_pss.hip): m is not compared but written out as
+// (28 L + 31) / 32 little-endian 32-bit words, SoA with stride `cnt` like base
+// (word j of lane t at mout[j cnt + t]), and the record gets RSA_MISMATCH until
+// k_rsa_pss decides; msgs / msg_offs are not read.
+template <int L, bool UNI = false, bool STORE = false>
 CESS_RSA_D void rsa_verify_lane(uint32_t t, uint32_t cnt, const uint32_t* __restrict__ rec,
                                 const uint32_t* __restrict__ key_idx, const RsaKeyDev* __restrict__ keys,
                                 const uint8_t* __restrict__ sigs, const uint64_t* __restrict__ sig_offs,
                                 const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_offs,
-                                uint32_t* __restrict__ base, uint8_t* __restrict__ codes) {
+                                uint32_t* __restrict__ base, uint8_t* __restrict__ codes,
+                                uint32_t* __restrict__ mout = nullptr) {
   const uint32_t r = rec[t];
   if (r == RSA_PAD) return;
   const uint32_t ki = key_idx[r];
@@ -248,6 +253,15 @@ CESS_RSA_D void rsa_verify_lane(uint32_t t, uint32_t cnt, const uint32_t* __rest
     mont<L, false>(x, one, n, K.ninv, x);
   }
   canon<L>(x, n);
+  if constexpr (STORE) {
+    constexpr int WS = (28 * L + 31) / 32;
+    uint32_t ws[WS];
+    to_words<L, WS>(x, ws);
+#pragma unroll
+    for (int j = 0; j < WS; j++) mout[(uint64_t)j * cnt + t] = ws[j];
+    codes[r] = RSA_MISMATCH;
+    return;
+  }
   // EM = I2OSP(m, k) == 0x00 0x01 0xff.. 0x00 || msg, compared byte by byte
   // from the least significant end (byte i is EM[k - 1 - i])
   const uint8_t* msg = msgs + msg_offs[r];
@@ -297,5 +311,17 @@ CESS_RSA_D void rsa_verify_lane(uint32_t t, uint32_t cnt, const uint32_t* __rest
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;                                                        \
     if (t >= *cnt) return;                                                                                           \
     rsa_verify_lane<L, true>(t, n_max, rec, key_idx, keys, sigs, sig_offs, msgs, msg_offs, base, codes);            \
+  }
+// store mode (RSASSA-PSS): no messages, m into mout (SoA of stride n_max)
+#define CESS_RSA_KERNEL_M(NAME, L, WAVES, UNI)                                                                       \
+  __global__ __launch_bounds__(256, WAVES) void NAME(                                                                \
+      uint32_t n_max, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ rec,                            \
+      const uint32_t* __restrict__ key_idx, const RsaKeyDev* __restrict__ keys, const uint8_t* __restrict__ sigs,   \
+      const uint64_t* __restrict__ sig_offs, uint32_t* __restrict__ base, uint8_t* __restrict__ codes,              \
+      uint32_t* __restrict__ mout) {                                                                                 \
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;                                                        \
+    if (t >= *cnt) return;                                                                                           \
+    rsa_verify_lane<L, UNI, true>(t, n_max, rec, key_idx, keys, sigs, sig_offs, nullptr, nullptr, base, codes,      \
+                                  mout);                                                                             \
   }
 #endif

@@ -23,6 +23,19 @@ using namespace rsa_big;
 
 // rec: this class's record list (its length at *cnt), key_idx / keys / the
 // record buffers as k_rsa_verify_2048.  One lane per record.
+// With CESS_RSA_BIG_STORE (k_rsa_bigm.hip, RSASSA-PSS) the same source is
+// k_rsa_verify_bigm: no messages; m is written out as ceil(k / 4)
+// little-endian 32-bit words, word j of lane t at mout[j n_max + t], for
+// k_rsa_pss, and the record gets RSA_MISMATCH until that kernel decides.
+#if defined(CESS_RSA_BIG_STORE)
+__global__ __launch_bounds__(256) void k_rsa_verify_bigm(uint32_t n_max, const uint32_t* __restrict__ cnt,
+                                                         const uint32_t* __restrict__ rec,
+                                                         const uint32_t* __restrict__ key_idx,
+                                                         const RsaKeyDev* __restrict__ keys,
+                                                         const uint8_t* __restrict__ sigs,
+                                                         const uint64_t* __restrict__ sig_offs,
+                                                         uint8_t* __restrict__ codes, uint32_t* __restrict__ mout) {
+#else
 __global__ __launch_bounds__(256) void k_rsa_verify_big(uint32_t n_max, const uint32_t* __restrict__ cnt,
                                                         const uint32_t* __restrict__ rec,
                                                         const uint32_t* __restrict__ key_idx,
@@ -32,6 +45,7 @@ __global__ __launch_bounds__(256) void k_rsa_verify_big(uint32_t n_max, const ui
                                                         const uint8_t* __restrict__ msgs,
                                                         const uint64_t* __restrict__ msg_offs,
                                                         uint8_t* __restrict__ codes) {
+#endif
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= *cnt || t >= n_max) return;
   const uint32_t r = rec[t];
@@ -85,6 +99,17 @@ __global__ __launch_bounds__(256) void k_rsa_verify_big(uint32_t n_max, const ui
     if (br)
       for (int i = 0; i < L; i++) x[i] = y[i];
   }
+#if defined(CESS_RSA_BIG_STORE)
+  // word j = bits [32 j, 32 j + 32) of m (m < n < 2^(8 k): nothing above word ceil(k / 4) - 1)
+  for (int j = 0; j < (kb + 3) / 4; j++) {
+    const int bit = 32 * j, li = bit / 28, sh = bit % 28;
+    uint32_t w = li < L ? x[li] >> sh : 0u;
+    if (li + 1 < L) w |= x[li + 1] << (28 - sh);
+    if (sh > 24 && li + 2 < L) w |= x[li + 2] << (56 - sh);
+    mout[(uint64_t)j * n_max + t] = w;
+  }
+  codes[r] = RSA_MISMATCH;
+#else
   // EM = I2OSP(m, k) == 0x00 0x01 0xff.. 0x00 || msg: byte i from the least
   // significant end is EM[kb - 1 - i]; every bit of m above 8 kb must be zero
   const uint8_t* msg = msgs + msg_offs[r];
@@ -106,4 +131,5 @@ __global__ __launch_bounds__(256) void k_rsa_verify_big(uint32_t n_max, const ui
     ok = ok && got == want;
   }
   codes[r] = ok ? RSA_OK : RSA_MISMATCH;
+#endif
 }

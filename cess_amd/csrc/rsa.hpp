@@ -29,7 +29,7 @@ struct RsaKeyDev {
   uint32_t k_bytes;       // byte length of n
   uint32_t ninv;          // -n^-1 mod 2^28
   uint32_t limbs;         // size class L
-  uint32_t pad;
+  uint32_t mod_bits;      // bit length of n (k_rsa_pss; the former padding word, so the row's layout stands)
   uint64_t e;             // public exponent (2 <= e < 2^33)
   uint32_t n28[RSA_LMAX];     // n, 28-bit limbs, little-endian
   uint32_t r2_28[RSA_LMAX];   // R^2 mod n, R = 2^(28 L)

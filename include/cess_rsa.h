@@ -205,6 +205,76 @@ int cess_rsa_verify_alg(cess_bls_ctx* ctx, int alg, const uint8_t* key_der, size
 int cess_sha2_batch(cess_bls_ctx* ctx, int digest, size_t n, const uint8_t* msgs, const uint64_t* msg_offsets,
                     uint8_t* out);
 
+/* ---------------------------------------------------------------------------
+ * RSASSA-PSS: ring's RSA_PSS_2048_8192_SHA256 / _SHA384 / _SHA512 (webpki's
+ * RSA_PSS_2048_8192_*_LEGACY_KEY), hashed and checked on the GPU.  Same
+ * exponentiation, key table and digest kernels as above; the check after
+ * m = s^e mod n is EMSA-PSS-VERIFY (k_rsa_pss) as ring does it
+ * (utils/ring/src/rsa/padding.rs:307-487): MGF1 over the same digest H, and a
+ * salt of exactly h = len(H) bytes -- a signature that RFC 8017 accepts with
+ * any other salt length fails.  With k the byte length of n:
+ *   len(sig) != k -> SIG_LEN;  s >= n -> SIG_RANGE;  then, all MISMATCH:
+ *   em_len = ceil((mod_bits - 1) / 8); where 8 divides mod_bits - 1, the first
+ *   byte of m must be 0 and EM is the rest; EM = maskedDB || H' || 0xbc;
+ *   the bits of maskedDB[0] above mod_bits - 1 must be 0;
+ *   DB = maskedDB xor MGF1(H', len) with those bits cleared must be
+ *   00 .. 00 01 || salt (h bytes);  H(00 x 8 || H(msg) || salt) == H'.
+ * ring also rejects s == 0; here 0^e = 0 has no 0xbc trailer, so that record
+ * is MISMATCH as well.  Precedence: KEY, SIG_LEN, SIG_RANGE, MISMATCH;
+ * CESS_RSA_MSG_LEN is never produced.
+ * Key policy: CESS_RSA_POLICY_RING_2048_8192, unchanged (the one-record entry
+ * loads the key under it; the batch entries run over whatever table is
+ * loaded).  A key below ring's floor (byte length under 256, i.e. under 2041
+ * bits) -- which only another policy lets into a table and which every ring
+ * PSS algorithm rejects -- gives CESS_RSA_KEY for its records of the right
+ * signature length (the front end has answered SIG_LEN for the others).
+ * `digest` is CESS_RSA_DIGEST_*; an unknown value is CESS_BLS_E_INVALID_ARG.
+ * The CESS_RSA_ALG_* numbering and cess_rsa_verify_alg do not cover PSS.
+ * ------------------------------------------------------------------------- */
+
+/* Arguments, codes_out / bitmap_out and multi-device sharding as
+ * cess_rsa_verify_digest_batch.  Host buffers. */
+int cess_rsa_verify_pss_batch(cess_bls_ctx* ctx, int digest, size_t n, const uint32_t* key_idx, const uint8_t* sigs,
+                              const uint64_t* sig_offsets, const uint8_t* msgs, const uint64_t* msg_offsets,
+                              uint8_t* codes_out, uint64_t* bitmap_out);
+
+/* Device-resident form: pointers, stream, the ordering of d_msg_offsets and
+ * the read bounds exactly as cess_rsa_verify_digest_batch_device (message
+ * bytes are fetched as whole aligned dwords, and only dwords that hold a
+ * message byte: up to 3 bytes before d_msgs if it is not 4-byte aligned and
+ * up to 3 bytes past d_msgs + d_msg_offsets[n], never beyond the aligned dword
+ * of the first / last byte). */
+int cess_rsa_verify_pss_batch_device(cess_bls_ctx* ctx, int digest, size_t n, const uint32_t* d_key_idx,
+                                     const uint8_t* d_sigs, const uint64_t* d_sig_offsets, const uint8_t* d_msgs,
+                                     const uint64_t* d_msg_offsets, uint8_t* d_codes, void* stream);
+
+/* verify_signature(&RSA_PSS_2048_8192_<digest>, msg, sig) drop-in for one
+ * record: the key, in `format`, is loaded under CESS_RSA_POLICY_RING_2048_8192.
+ * CESS_BLS_E_BAD_KEY where ring rejects the key, CESS_RSA_E_UNSUPPORTED where
+ * the GPU cannot verify it (a modulus the loop-form size class does not hold:
+ * above 4112 bits); else *ok_out = the verdict. */
+int cess_rsa_verify_pss(cess_bls_ctx* ctx, int digest, const uint8_t* key_der, size_t key_len, int format,
+                        const uint8_t* msg, size_t msg_len, const uint8_t* sig, size_t sig_len, int* ok_out);
+
+/* The EM check alone, exposed for tests (like cess_sha2_batch): record i is
+ * the message value m_i = ems[em_offsets[i] .. [i+1]) (big-endian, as
+ * s^e mod n would be) of a modulus of mod_bits[i] <= 4112 bits (the largest
+ * the loop-form size class holds), and
+ * H(msg_i) = digests[h i .. h i + h).  codes_out (n): CESS_RSA_OK or
+ * CESS_RSA_MISMATCH; an m_i that is not ceil(mod_bits[i] / 8) bytes long is a
+ * MISMATCH (ring reads m to its end).  Host buffers. */
+int cess_rsa_pss_em_batch(cess_bls_ctx* ctx, int digest, size_t n, const uint32_t* mod_bits, const uint8_t* ems,
+                          const uint64_t* em_offsets, const uint8_t* digests, uint8_t* codes_out);
+
+/* cess_bls_stage_stats for the stages that are RSASSA-PSS's own: the EM check
+ * as "k_rsa_pss" when the call took the unsorted class lists and "k_rsa_pss_u"
+ * when it took the key-uniform ones (either includes the launch that marks
+ * 1024-bit-class records; the digest, classify and exponentiation launches are
+ * counted under k_rsa_digest, k_rsa_classify and k_rsa_verify of
+ * cess_bls_stage_stats). */
+int cess_rsa_pss_stage_stats(cess_bls_ctx* ctx, const char** names, double* ms, uint64_t* launches, int max,
+                             int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,24 @@ extern "C" {
     pub fn cess_sha2_batch(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, msgs: *const u8, msg_offsets: *const u64,
                            out: *mut u8) -> c_int;
 
+    // RSASSA-PSS: ring's RSA_PSS_2048_8192_SHA256 / _SHA384 / _SHA512 (salt length = digest length); no node
+    // host function is wired to it (verify_miner_cert's SUPPORTED_SIG_ALGS lists no PSS algorithm)
+    pub fn cess_rsa_verify_pss_batch(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, key_idx: *const u32,
+                                     sigs: *const u8, sig_offsets: *const u64, msgs: *const u8,
+                                     msg_offsets: *const u64, codes_out: *mut u8, bitmap_out: *mut u64) -> c_int;
+    pub fn cess_rsa_verify_pss_batch_device(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, d_key_idx: *const u32,
+                                            d_sigs: *const u8, d_sig_offsets: *const u64, d_msgs: *const u8,
+                                            d_msg_offsets: *const u64, d_codes: *mut u8,
+                                            stream: *mut c_void) -> c_int;
+    pub fn cess_rsa_verify_pss(ctx: *mut cess_bls_ctx, digest: c_int, key_der: *const u8, key_len: usize,
+                               format: c_int, msg: *const u8, msg_len: usize, sig: *const u8, sig_len: usize,
+                               ok_out: *mut c_int) -> c_int;
+    pub fn cess_rsa_pss_em_batch(ctx: *mut cess_bls_ctx, digest: c_int, n: usize, mod_bits: *const u32,
+                                 ems: *const u8, em_offsets: *const u64, digests: *const u8,
+                                 codes_out: *mut u8) -> c_int;
+    pub fn cess_rsa_pss_stage_stats(ctx: *mut cess_bls_ctx, names: *mut *const c_char, ms: *mut f64,
+                                    launches: *mut u64, max: c_int, reset: c_int) -> c_int;
+
     // include/cess_ed25519.h: batch Ed25519 under ring's ED25519 rules (NodePublicKey / NodeSignature,
     // primitives/common/src/lib.rs:73-74); no node host function is wired to it
     pub fn cess_ed25519_keys_load(ctx: *mut cess_bls_ctx, k: usize, keys: *const u8, key_offsets: *const u64,

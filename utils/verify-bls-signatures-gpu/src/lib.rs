@@ -438,6 +438,36 @@ impl Verifier {
         Ok(ok != 0)
     }
 
+    /// RSASSA-PSS under ring's RSA_PSS_2048_8192_SHA256 / _SHA384 / _SHA512
+    /// (`digest`: ffi::CESS_RSA_DIGEST_*; salt length = digest length) over a
+    /// batch against the loaded key table; codes as verify_rsa_batch.
+    pub fn verify_rsa_pss_batch(&mut self, digest: i32, key_idx: &[u32], msgs: &[&[u8]],
+                                sigs: &[&[u8]]) -> Result<Verdicts, Error> {
+        assert!(key_idx.len() == msgs.len() && msgs.len() == sigs.len());
+        let n = key_idx.len();
+        let (mut md, mut sd) = (Vec::new(), Vec::new());
+        let mo = offsets(msgs.iter().copied(), &mut md);
+        let so = offsets(sigs.iter().copied(), &mut sd);
+        let mut codes = vec![0u8; n];
+        let mut bitmap = vec![0u64; (n + 63) / 64];
+        check(unsafe {
+            ffi::cess_rsa_verify_pss_batch(self.ctx, digest as c_int, n, key_idx.as_ptr(), sd.as_ptr(), so.as_ptr(),
+                                           md.as_ptr(), mo.as_ptr(), codes.as_mut_ptr(), bitmap.as_mut_ptr())
+        })?;
+        Ok(Verdicts { bitmap, codes })
+    }
+
+    /// verify_signature(&RSA_PSS_2048_8192_<digest>, msg, sig) for one record,
+    /// the key in `format` loaded under ring's 2048..8192-bit key policy.
+    pub fn verify_rsa_pss(&mut self, digest: i32, key_der: &[u8], format: i32, msg: &[u8], sig: &[u8]) -> Result<bool, Error> {
+        let mut ok: c_int = 0;
+        check(unsafe {
+            ffi::cess_rsa_verify_pss(self.ctx, digest as c_int, key_der.as_ptr(), key_der.len(), format as c_int,
+                                     msg.as_ptr(), msg.len(), sig.as_ptr(), sig.len(), &mut ok)
+        })?;
+        Ok(ok != 0)
+    }
+
     // --- generators (PrivateKey::public_key / sign, src/lib.rs:226-236) -------
     pub fn public_keys(&mut self, sks: &[[u8; 32]]) -> Result<Vec<[u8; 96]>, Error> {
         let flat: Vec<u8> = sks.iter().flat_map(|k| k.iter().copied()).collect();
