@@ -844,7 +844,8 @@ extern "C" int cess_rsa_pss_em_batch(cess_bls_ctx* c, int digest, size_t n, cons
   if (n == 0) return CESS_BLS_OK;
   if (!mod_bits || !em_offsets || !digests || !codes_out || n >= (1ull << 31)) return CESS_BLS_E_INVALID_ARG;
   // ring reads m to its end: a length other than k is a mismatch, decided here;
-  // the others are the kernel's list, with m as words (word j of record r at j n + r)
+  // the others are the kernel's list, with m as words (word j of list entry t at
+  // j n + t, as the store-mode kernels leave it: t < r once a record was left out)
   std::vector<uint8_t> codes(n, RSA_MISMATCH);
   std::vector<uint32_t> list, m((size_t)kPssWordsBig * n, 0);
   for (size_t r = 0; r < n; r++) {
@@ -853,7 +854,8 @@ extern "C" int cess_rsa_pss_em_batch(cess_bls_ctx* c, int digest, size_t n, cons
     if (len != k) continue;
     if (!ems) return CESS_BLS_E_INVALID_ARG;
     const uint8_t* em = ems + em_offsets[r];
-    for (uint64_t i = 0; i < k; i++) m[(i >> 2) * n + r] |= (uint32_t)em[k - 1 - i] << (8 * (i & 3));
+    const size_t t = list.size();
+    for (uint64_t i = 0; i < k; i++) m[(i >> 2) * n + t] |= (uint32_t)em[k - 1 - i] << (8 * (i & 3));
     list.push_back((uint32_t)r);
   }
   const uint32_t cnt = (uint32_t)list.size();

@@ -99,7 +99,7 @@ int main(int argc, char** argv) {
       need(16 + lw);
       std::vector<uint8_t> mh(h), em(len);
       memcpy(mh.data(), &in[p], h);
-      memcpy(em.data(), in.data() + p + 16, len);
+      if (len) memcpy(em.data(), in.data() + p + 16, len);   // (an empty record: no bytes, and no pointer to copy to)
       p += 16 + lw;
       res.push_back((uint32_t)emu_rsa_pss_em((int)digest, bits, em.data(), len, mh.data()));
     } else if (kind == 1) {

@@ -34,7 +34,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 GPU_MAX_BITS = 4112      # the loop-form size class holds 8 k + 2 <= 28 x 147 bits: k <= 514 bytes
 
 
-# The two fixtures are hex-heavy JSON (ring_rsa_pss.json.gz, rsa_pss_edges.json.gz): kept gzipped, written
+# The fixtures are hex-heavy JSON (ring_rsa_pss.json.gz, rsa_pss_edges.json.gz, rsa_pss_phase_keys.json.gz): kept gzipped, written
 # without a time stamp so that regenerating them gives the same bytes.  `zcat FILE | python -m json.tool` reads one.
 # Beside each lies NAME.codes.txt, one line per row with what identifies the row and its recorded code: the part
 # of a fixture that a diff should show.  tests/test_rsa_pss.py holds the two together.

@@ -4,8 +4,11 @@ The plain-Python model (tests/rsa_pss_model.py) against both sets of ring rows a
 recorded codes; cess_amd/csrc/rsa_pss.hpp built for the host (tests/hostemu/rsa_pss_emu.cpp) against the
 model on ring's padding rows, on every edge row (m by pow) and on random m with one byte changed at every
 position; the one-record path (the 2048-bit class's exponentiation in store mode, then the EM check) on the
-host; the same rows once more in a stand-alone program under the address and undefined-behaviour
-sanitizers; the code-object notes of the new and the old kernels; the bindings."""
+host; the sweep of tests/rsa_pss_sweep.py (every byte phase, top mask, separator position and salt-mask
+offset, one changed bit at every byte position) through the same host build; the phase-key fixture against
+the model and its keys of the compile-time class through the one-record path; the same rows once more in a
+stand-alone program under the address and undefined-behaviour sanitizers; the code-object notes of the new
+and the old kernels; the bindings."""
 import ctypes
 import glob
 import hashlib
@@ -24,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import rsa_probe_model as pm  # noqa: E402
 import rsa_pss_model as model  # noqa: E402
+import rsa_pss_sweep as sweep  # noqa: E402
 
 CSRC = os.path.join(ROOT, "cess_amd", "csrc")
 SRC = os.path.join(ROOT, "tests", "hostemu", "rsa_pss_emu.cpp")
@@ -42,6 +46,14 @@ def ring():
 @pytest.fixture(scope="module")
 def edges():
     fx = model.load_fixture("rsa_pss_edges.json.gz")
+    for k in fx["keys"]:
+        k["n"], k["e"] = int(k["n"], 16), int(k["e"], 16)
+    return fx
+
+
+@pytest.fixture(scope="module")
+def phase():
+    fx = model.load_fixture("rsa_pss_phase_keys.json.gz")
     for k in fx["keys"]:
         k["n"], k["e"] = int(k["n"], 16), int(k["e"], 16)
     return fx
@@ -111,9 +123,35 @@ def test_model_against_edge_fixture(edges):
     assert (257 - 32 - 1) % 32 == 0 and (257 - 64 - 1) % 64 == 0 and (289 - 48 - 1) % 48 == 0
 
 
+def test_model_against_phase_key_fixture(phase, edges):
+    """the keys for the phases and class edges that the edge fixture's keys do not reach: sizes, classes, the
+    model's code of every row, the cases per key, and d (to sign with) for the compile-time class alone"""
+    keys, table = phase["keys"], phase["table"]
+    assert [(k["name"], k["bits"]) for k in keys] == [("p2058", 2058), ("p2065", 2065), ("p2070", 2070), ("p3090", 3090),
+                                                      ("p4112", 4112)]
+    assert [model.key_status(bytes.fromhex(t["der"]))[0] for t in table] == [t["status"] for t in table] == ["ok"] * 5
+    for k, t in zip(keys, table):
+        assert model.ring_key(bytes.fromhex(t["der"])) == (k["n"], k["e"]) and k["n"].bit_length() == k["bits"]
+        L = pm.size_class_limbs(k["bits"], (k["bits"] + 7) // 8)
+        assert (L == L2048) == (k["bits"] <= 2070) == ("d" in k) and L
+        if "d" in k:
+            assert pow(pow(12345, int(k["d"], 16), k["n"]), k["e"], k["n"]) == 12345
+    assert [((k["bits"] + 7) // 8, (k["bits"] + 6) // 8 & 3) for k in keys] == [(258, 2), (259, 2), (259, 3), (387, 3), (514, 2)]
+    assert pm.size_class_limbs(2071, 259) > L2048 and pm.size_class_limbs(4113, 515) == 0
+    assert not {k["bits"] for k in keys} & {k["bits"] for k in edges["keys"]}
+    cases = {}
+    for r in phase["rows"]:
+        k = keys[r["key"]]
+        code = model.verify_code(r["digest"], k["n"], k["e"], bytes.fromhex(r["msg"]), bytes.fromhex(r["sig"]))
+        assert code == r["code"] and (code == OK) == (r["case"] == "valid"), (r["digest"], k["name"], r["case"])
+        cases.setdefault((r["digest"], k["name"]), []).append(r["case"])
+    core = ["valid", "above_em_bits", "ps_first", "sep_02", "salt_changed", "hprime_changed"]
+    assert cases == {(d, k["name"]): core + (["leading_byte"] if k["name"] == "p2065" else []) for d in DIGESTS for k in keys}
+
+
 def test_code_lists_beside_the_fixtures(ring, edges):
     """NAME.codes.txt, the text that shows each row's recorded code in a diff, is what the gzipped fixture holds"""
-    for name in ("ring_rsa_pss.json.gz", "rsa_pss_edges.json.gz"):
+    for name in ("ring_rsa_pss.json.gz", "rsa_pss_edges.json.gz", "rsa_pss_phase_keys.json.gz"):
         with open(model.codes_path(name)) as f:
             assert f.read().splitlines() == model.code_lines(model.load_fixture(name)), name
 
@@ -129,16 +167,17 @@ def test_header_on_ring_padding_rows(ring):
     assert n == 80
 
 
-def test_header_on_edge_rows(edges):
-    seen = set()
-    for r in edges["rows"]:
-        if r["code"] not in (OK, MISMATCH):
-            continue
-        k = edges["keys"][r["key"]]
-        m = pow(int(r["sig"], 16), k["e"], k["n"]).to_bytes((k["bits"] + 7) // 8, "big")
-        assert emu_em(r["digest"], k["bits"], m, bytes.fromhex(r["msg"])) == r["code"], (r["digest"], k["name"], r["case"])
-        seen.add((k["name"], r["code"]))
-    assert all((k["name"], c) in seen for k in edges["keys"] for c in (OK, MISMATCH))
+def test_header_on_edge_rows(edges, phase):
+    for fx in (edges, phase):
+        seen = set()
+        for r in fx["rows"]:
+            if r["code"] not in (OK, MISMATCH):
+                continue
+            k = fx["keys"][r["key"]]
+            m = pow(int(r["sig"], 16), k["e"], k["n"]).to_bytes((k["bits"] + 7) // 8, "big")
+            assert emu_em(r["digest"], k["bits"], m, bytes.fromhex(r["msg"])) == r["code"], (r["digest"], k["name"], r["case"])
+            seen.add((k["name"], r["code"]))
+        assert all((k["name"], c) in seen for k in fx["keys"] for c in (OK, MISMATCH))
 
 
 @pytest.mark.parametrize("name", DIGESTS)
@@ -176,30 +215,46 @@ def test_header_on_changed_bytes(name):
     assert emu_em(name, small - 8, bytes(2 * h + 1), b"") == MISMATCH == model.em_code(name, b"", bytes(2 * h + 1), small - 8)
 
 
+@pytest.mark.parametrize("name", DIGESTS)
+def test_header_on_the_sweep(name):
+    """every record of tests/rsa_pss_sweep.py: all 32 pairs (em_len & 3, em_bits & 7) at the smallest sizes, at
+    2041..2072 and at 4081..4112 bits, ps_len 0..11, r in {1, 2, 3, 4, h - 1, h}, the sizes with no valid encoding;
+    per size three valid encodings, one changed bit at every byte position, the edge fixture's crafted cases and
+    the wrong lengths.  The code of each is the model's."""
+    e, dg = emu(), model.DIGEST_ID[name]
+    recs = sweep.sweep(name)
+    bad = [sweep.where(r) + (got,) for r in recs
+           for got in [e.emu_rsa_pss_em(dg, r[0], r[1], len(r[1]), r[2])] if got != (OK if r[3] else MISMATCH)]
+    assert not bad, (len(bad), bad[:20])
+    assert len(recs) > 30000 and sum(r[3] for r in recs) == 3 * sum(sweep.metrics(name, b)["valid"] for b in sweep.sizes(name))
+
+
 # --- the one-record path on the host --------------------------------------------------------------------
 def key_row(n):
     L = pm.size_class_limbs(n.bit_length(), (n.bit_length() + 7) // 8)
     return L, pm.limbs(n, L), pm.limbs(pow(2, 2 * 28 * L, n), L), pm.ninv_of(n)
 
 
-def one_record_rows(ring, edges):
+def one_record_rows(ring, edges, phase):
     """(digest, n, e, msg, sig, code) of every fixture row of the 2048-bit size class that reaches a kernel"""
     out = []
     for r in ring["verify"]:
         n, e = model.ring_key(bytes.fromhex(r["key"]))
         out.append((r["digest"], n, e, bytes.fromhex(r["msg"]), bytes.fromhex(r["sig"]), r["code"]))
-    for r in edges["rows"]:
-        if r["key"] < len(edges["keys"]) and r["code"] != SIG_LEN:
-            k = edges["keys"][r["key"]]
-            if key_row(k["n"])[0] == L2048:
-                out.append((r["digest"], k["n"], k["e"], bytes.fromhex(r["msg"]), bytes.fromhex(r["sig"]), r["code"]))
+    for fx in (edges, phase):
+        for r in fx["rows"]:
+            if r["key"] < len(fx["keys"]) and r["code"] != SIG_LEN:
+                k = fx["keys"][r["key"]]
+                if key_row(k["n"])[0] == L2048:
+                    out.append((r["digest"], k["n"], k["e"], bytes.fromhex(r["msg"]), bytes.fromhex(r["sig"]), r["code"]))
     return out
 
 
-def test_one_record_path_on_host(ring, edges):
+def test_one_record_path_on_host(ring, edges, phase):
+    """(with the phase keys: m of 65 words, a leading zero byte in word 64, the largest key of the class)"""
     e = emu()
     arr = lambda v: np.array(v, dtype=np.uint32)   # noqa: E731
-    rows = one_record_rows(ring, edges)
+    rows = one_record_rows(ring, edges, phase)
     rowcache = {}
     for name, n, ex, msg, sig, code in rows:
         if n not in rowcache:
@@ -211,14 +266,15 @@ def test_one_record_path_on_host(ring, edges):
                                    n28.ctypes.data_as(ctypes.c_void_p), r2.ctypes.data_as(ctypes.c_void_p), ninv, sig,
                                    model.HASH[name](msg).digest())
         assert got == code, (name, n.bit_length(), code, got)
-    assert {n.bit_length() for _, n, *_ in rows} == {2041, 2048, 2049, 2056}
-    assert {c for *_, c in rows} == {OK, SIG_RANGE, MISMATCH} and len(rows) > 150
+    assert {n.bit_length() for _, n, *_ in rows} == {2041, 2048, 2049, 2056, 2058, 2065, 2070}
+    assert {c for *_, c in rows} == {OK, SIG_RANGE, MISMATCH} and len(rows) > 150 + 57
 
 
-def test_rows_under_sanitizers(tmp_path, ring, edges):
+def test_rows_under_sanitizers(tmp_path, ring, edges, phase):
     """rsa_pss_emu.cpp as a stand-alone program (its own main, run as a child process; the test preloads nothing)
-    built with the address and undefined-behaviour sanitizers: ring's padding rows, the edge rows' m and the
-    one-record rows once more"""
+    built with the address and undefined-behaviour sanitizers: ring's padding rows, the edge rows' m, the
+    one-record rows (the phase keys' among them) and the sweep's records of the smallest valid size, 2058, 2070
+    and 4112 bits once more"""
     exe = str(tmp_path / "rsa_pss_emu_san")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-fno-omit-frame-pointer", "-DCESS_HOSTEMU", "-DRSA_PSS_EMU_MAIN",
                            "-fsanitize=address,undefined", "-fno-sanitize-recover=all", SRC, "-o", exe])
@@ -242,7 +298,12 @@ def test_rows_under_sanitizers(tmp_path, ring, edges):
             blob.append(struct.pack("<4I", 0, model.DIGEST_ID[r["digest"]], k["bits"], len(m)) + mh + bytes(64 - len(mh)) +
                         padded(m))
             want.append(r["code"])
-    for name, n, ex, msg, sig, code in one_record_rows(ring, edges):
+    for name in DIGESTS:
+        for bits, em, mh, ok, _ in sweep.subset(name, (sweep.smallest(name), 2058, 2070, 4112)):
+            blob.append(struct.pack("<4I", 0, model.DIGEST_ID[name], bits, len(em)) + mh + bytes(64 - len(mh)) + padded(em))
+            want.append(OK if ok else MISMATCH)
+    assert len(want) > 3 * 1100 and want.count(OK) > 3 * 12
+    for name, n, ex, msg, sig, code in one_record_rows(ring, edges, phase):
         L, n28, r2, ninv = key_row(n)
         mh = model.HASH[name](msg).digest()
         blob.append(struct.pack("<4I", 1, model.DIGEST_ID[name], n.bit_length(), len(sig)) +
